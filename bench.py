@@ -6,7 +6,11 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
     one rank per GPU, RCCL data parallel (RANK/LOCAL_RANK/WORLD_SIZE from env).
   * W untimed warmup steps, then EXACTLY K timed optimizer steps bracketed by a
     barrier + device synchronize on both sides; the time is the MAX over ranks.
-  * rank 0 prints ONE JSON line.
+  * rank 0 prints ONE JSON line; ``ms_per_step`` in it is the time of one timed step.
+  * ``--dump-outputs DIR``: rank 0 also writes what the last timed step returned, its loss, as
+    DIR/loss.npy; the same arguments give the same inputs every run
+    (seeded weights, seeded synthetic shard, seeded loader), so two builds compare output for output.
+  * ``--full``: secondary measurements (none today); a plain run does only the above.
 Every timed step is a full training step: synthetic tokens streamed by the
 native loader (pinned, side-stream H2D), forward, backward, bucketed RCCL
 all-reduce overlapped with backward, fused AdamW on fp32 masters, zero_grad.
@@ -76,7 +80,24 @@ def parse(argv=None):
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: functional rehearsal on gloo (fp32, tiny shapes); never a measurement")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy: "
+                         "loss.npy, its loss (float32, one element)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement; a plain run only sets up, warms up, times --steps "
+                         "steps and prints the result line. This benchmark has no secondary measurement, so --full "
+                         "changes nothing today; new ones belong behind it")
     return ap.parse_args(argv)
+
+
+def dump_outputs(dst: str, loss: float) -> None:
+    """--dump-outputs: what the last timed step handed back to its caller, one .npy per array.  A training
+    step returns its loss and nothing else.  (The weights it leaves are not written: the bf16 step is not
+    bit-reproducible from run to run, and after 25 AdamW steps single weights differed by up to one
+    learning-rate step, 5.6e-4, between two runs of the same build on MI355X; the loss by 6e-6.)"""
+    import numpy as np
+    os.makedirs(dst, exist_ok=True)
+    np.save(os.path.join(dst, "loss.npy"), np.asarray([loss], dtype=np.float32))
 
 
 def _free_port() -> int:
@@ -222,6 +243,8 @@ def main(argv=None):
     elapsed = time.perf_counter() - t0
     final_loss = float(loss.detach())
     opt.wait_params()
+    if args.dump_outputs and di.is_master:
+        dump_outputs(args.dump_outputs, final_loss)
     ctime = engine.timer.report()
     rank_ms = [1000 * elapsed / args.steps]
     exposed = [ctime.get("exposed_comm_ms") or 0.0]

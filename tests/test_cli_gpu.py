@@ -3,6 +3,7 @@ the training CLI with a preset (HIP kernels, periodic checkpoint), generate_text
 checkpoint, and the self-launching multi-rank bench (2 ranks sharing the one GPU over gloo: the
 functional rehearsal of the driver's N-GPU run)."""
 import json
+import math
 import os
 import subprocess
 import sys
@@ -33,6 +34,26 @@ def test_train_cli_and_generate_gpu(tmp_path):
               "--seed", "1"])
     assert g.returncode == 0, g.stderr[-3000:]
     assert "Generated text:" in g.stdout
+
+
+def test_bench_dump_outputs_gpu(tmp_path):
+    """A plain one-GPU run (graph-replayed step on the HIP kernels): --steps timed steps, ms_per_step in
+    the result line, and --dump-outputs leaves the last step's loss."""
+    import numpy as np
+    r = _run(["bench.py", "--gpus", "1", "--model", "gpt2-tiny", "--steps", "3", "--warmup", "1", "--batch", "4",
+              "--seq", "128", "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    recs = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(recs) == 1, r.stdout
+    rec = recs[0]
+    assert rec["steps"] == 3 and rec["device"] == "cuda" and rec["dtype"] == "bf16" and rec["config"]["backend"] == "auto"
+    assert rec["ms_per_step"] > 0 and abs(rec["value"] - 4 * 128 / (rec["ms_per_step"] / 1000)) / rec["value"] < 0.01
+    assert os.listdir(tmp_path / "out") == ["loss.npy"]
+    loss = np.load(tmp_path / "out" / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == (1,) and np.isfinite(loss).all()
+    assert abs(float(loss[0]) - rec["final_loss"]) < 1e-3  # (the record rounds to 4 places)
+    # random-init gpt2-tiny after 4 steps: still near ln(vocab)
+    assert 0.5 * math.log(50304) < float(loss[0]) < 1.5 * math.log(50304)
 
 
 def test_bench_two_ranks_one_gpu_gloo():
