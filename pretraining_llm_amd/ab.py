@@ -10,7 +10,6 @@ choice on the same box without a rebuild.  The C++ side reads the same variable 
 |---|---|---|---|
 | resid_gemm | 1 | 0: the block's residual add in the next norm instead of the projections' GEMMs | r5_residual_in_gemm.md |
 | wt_shadow | 1 | 0: data-gradient GEMMs on the weights as stored (no transposed shadows) | r1_prof6_gpt2small_b64_kernel_stats.md (the transposes it replaced) |
-| rope_prepass | 1 | 0: RoPE rotated inside the attention kernels' q / k staging | r2_rope_prepass_ab.txt |
 | attn_proj_fused | 1 | 0: attention output-projection backward on hipBLASLt + the delta pre-pass | r4_fusion_analysis.md |
 | fused_swiglu_fwd | 1 | 0: llama up-projection on hipBLASLt + the SwiGLU kernel | r4_gemm_pp.md |
 | lt_relu | 1 | 0: ReLU MLP up-projection on torch + the activation kernel | r4_lt_relu_epilogue.md |

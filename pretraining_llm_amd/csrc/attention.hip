@@ -12,8 +12,8 @@
 //    (MFMA operands that sum over D) and for ds_read_b64_tr_b16 transposed reads
 //    (operands that sum over rows), so one image serves both (guide §5.5 T2/T10).
 //  * forward: one workgroup = 4 waves, each owning 2 (D <= 64) or 1 (D = 128)
-//    blocks of 32 query rows, K/V tiles of 64 keys double-buffered in LDS through
-//    registers (issue-early / write-late, T14).
+//    blocks of 32 query rows, K/V tiles of 64 keys double-buffered in LDS by LDS DMA
+//    (the next tile's buffer_load ... lds issued before this tile's MFMAs).
 //    S^T = K.Q^T is computed with the QUERY on the MFMA lane, so the softmax row
 //    statistics (m, l) are per-lane scalars and the P^T accumulator is directly
 //    the B operand of O^T += V^T.P^T (no LDS round trip for P).
@@ -64,6 +64,9 @@ constexpr float kLazyThr = 8.f;
 // (no faster, r3_attn_fwd_experiments.md), an exponent-ready "V3" forward, the 8-wave D = 128 forward
 // (neutral, r4_attn_experiments.md), register-staged K/V tiles instead of LDS DMA in the forward, and in
 // the backward the spread / asymmetric Q-dO DMA issue and the wave-4-7 stagger (r4_attn_experiments.md).
+// RoPE inside the kernels (q / k rotated while staged through registers, tables read per tile) measured
+// +22 % forward / +25 % backward against one rope_qk pre-pass (the round-2 RoPE A/B record in profiles/) and is gone too:
+// q / k arrive rotated, the backward kernels only rotate dq / dk back while storing them.
 
 template <int D>
 struct FwdCfg {
@@ -76,7 +79,7 @@ struct FwdCfg {
   static constexpr int LDS_ELEMS = 4 * TILE;
 };
 
-template <int D, bool ROPE>
+template <int D>
 __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_kernel(AttnFwdArgs a) {
   using C = FwdCfg<D>;
   using I = Img<D>;
@@ -115,14 +118,6 @@ __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks)
       raw[ks] = qi < a.T ? ld16(qp + (int64_t)qi * a.q_st + 16 * ks + 8 * hh) : u32x4{0u, 0u, 0u, 0u};
-    if (ROPE && qi < a.T) {
-      // the lane's chunks ks and ks + NKS/2 hold head-dim elements i and i + D/2
-      const int64_t tab = (int64_t)(qi + off) * (D / 2);
-#pragma unroll
-      for (int ks = 0; ks < NKS / 2; ++ks)
-        rope8(raw[ks], raw[ks + NKS / 2], a.rope_cos + tab + 16 * ks + 8 * hh, a.rope_sin + tab + 16 * ks + 8 * hh,
-              1.f);
-    }
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) qf[j][ks] = as_frag(raw[ks]);
   }
@@ -132,51 +127,10 @@ __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_
   if (a.causal) kv_end = min(a.S, q0 + BM + off);
   const int ntiles = (kv_end + BN - 1) / BN;
 
-  // chunk i of this thread: row c / CPR, column chunk (c % CPR2) + (i odd ? CPR2 : 0) with
-  // c = tid + NTH * (i / 2) and CPR2 = CPR / 2, so a thread holds both RoPE partners of a row
-  constexpr int CPR2 = CPR / 2, NTH = 64 * NW;
-  constexpr int NPAIR = (BN * CPR2 + NTH - 1) / NTH;
-  u32x4 kr[2 * NPAIR], vr[2 * NPAIR];
-  // K / V rows by buffer loads through a per-tile descriptor (scalar base = the tile's first
-  // row): rows past S read as zeros (range check), per-lane offsets loop-invariant
-  auto gload = [&](int t) {
-    const int kv0 = t * BN;
-    const auto krs = rows_rsrc(kp + (int64_t)kv0 * a.k_st, a.S - kv0, a.k_st, D);
-    const auto vrs = rows_rsrc(vp + (int64_t)kv0 * a.v_st, a.S - kv0, a.v_st, D);
-#pragma unroll
-    for (int i = 0; i < 2 * NPAIR; ++i) {
-      const int c = tid + NTH * (i / 2), row = c / CPR2, col = c % CPR2 + (i & 1) * CPR2;
-      if (c < BN * CPR2) {
-        kr[i] = buf_ld16(krs, (uint32_t)(row * (int)a.k_st + col * 8) * 2u);
-        vr[i] = buf_ld16(vrs, (uint32_t)(row * (int)a.v_st + col * 8) * 2u);
-      } else {
-        kr[i] = u32x4{0u, 0u, 0u, 0u};
-        vr[i] = u32x4{0u, 0u, 0u, 0u};
-      }
-    }
-  };
-  auto swrite = [&](int buf, int t, int vbuf) {
-    uint16_t* Kb = smem + buf * TILE;
-    uint16_t* Vb = smem + 2 * TILE + vbuf * TILE;
-#pragma unroll
-    for (int i = 0; i < 2 * NPAIR; i += 2) {
-      const int c = tid + NTH * (i / 2), row = c / CPR2, col = c % CPR2;
-      if (c >= BN * CPR2) continue;
-      if (ROPE) {
-        const int key = t * BN + row;
-        const int64_t tab = (int64_t)min(key, a.S - 1) * (D / 2) + col * 8;
-        rope8(kr[i], kr[i + 1], a.rope_cos + tab, a.rope_sin + tab, 1.f);
-      }
-      I::st_pair(Kb, row, col, kr[i], kr[i + 1]);
-      I::st_pair(Vb, row, col, vr[i], vr[i + 1]);
-    }
-  };
-
-  // LDS DMA of the plain loop (no fused RoPE): each wave moves PPW 1-KiB pieces of the K then V
-  // tile straight into the swizzled image -- lane l of a piece fills LDS chunk 64 p + l, so it
-  // loads the logical chunk that the image stores there (row g / CPR, chunk (g % CPR) ^ f(row)).
-  // No staging registers, no ds_write restage; rows past S read as zeros (descriptor range).
-  constexpr bool DMA = !ROPE;
+  // K / V tiles by LDS DMA: each wave moves PPW 1-KiB pieces of the K then V tile straight into
+  // the swizzled image -- lane l of a piece fills LDS chunk 64 p + l, so it loads the logical
+  // chunk that the image stores there (row g / CPR, chunk (g % CPR) ^ f(row)).  No staging
+  // registers, no ds_write restage; rows past S read as zeros (descriptor range).
   constexpr int PCS = BN * CPR / 64;  // pieces per tile
   constexpr int PPW = 2 * PCS / NW;   // K + V pieces per wave
   static_assert(2 * PCS % NW == 0 && PCS % PPW == 0, "a wave's pieces lie in one operand");
@@ -226,13 +180,8 @@ __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_
   const uint64_t st_start = __builtin_amdgcn_s_memtime();
 #endif
   if (ntiles > 0) {
-    if constexpr (DMA) {
-      gdma(0, 0);
-      vm_wait_all();
-    } else {
-      gload(0);
-      swrite(0, 0, 0);
-    }
+    gdma(0, 0);
+    vm_wait_all();
   }
   __syncthreads();
   for (int t = 0; t < ntiles; ++t) {
@@ -248,10 +197,7 @@ __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_
 #define PL_STAMP(i)
 #endif
     const int buf = t & 1;
-    if (t + 1 < ntiles) {
-      if constexpr (DMA) gdma(t + 1, buf ^ 1);
-      else gload(t + 1);
-    }
+    if (t + 1 < ntiles) gdma(t + 1, buf ^ 1);
     PL_STAMP(0);
     const int kv0 = t * BN;
     // which of this wave's blocks see keys of this tile: a compile-time mask per code
@@ -370,8 +316,7 @@ __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_
     else if (mask == 1) tile(std::integral_constant<int, 1>{});
     else if (QB > 1 && mask == 2) tile(std::integral_constant<int, 2>{});
     PL_STAMP(3);
-    if constexpr (DMA) vm_wait_all();
-    else if (t + 1 < ntiles) swrite(buf ^ 1, t + 1, buf ^ 1);
+    vm_wait_all();
     PL_STAMP(4);
     __syncthreads();
     PL_STAMP(5);
@@ -432,7 +377,8 @@ __global__ __launch_bounds__(256) void attn_bwd_pre_kernel(AttnBwdArgs a) {
   if (row < nrows && c == 0) a.delta[((int64_t)b * a.H + h) * a.T + t] = acc;
 }
 
-// Fused-role backward tiling (D = 32 / 64; D = 128 runs the role-split kernel below): 8 waves
+// Fused-role backward tiling (D = 32 / 64; D = 128 runs the key-stationary kernel of attn_bwd_ks.hip or
+// the role-split kernel below): 8 waves
 // (two per SIMD), each owning 32 keys (BK = 256 keys per workgroup); BQ = 128 query rows per
 // iteration as NQB = 4 sub-blocks of 32.  KH (32-key halves per wave) stays a parameter of the
 // code.  Measured and removed (same-box A/B, profiles/r2_attn_bwd_removed_variants_ab.jsonl):
@@ -466,8 +412,9 @@ struct BwdCfg {
 // the slabs in fp32 in a fixed order (deterministic, no atomics) into an fp32 running sum / the
 // bf16 dQ.  fp32 slabs (no partial rounding) measured +12 % (T 1024, D 64) to +34 % (T 4096)
 // on the whole backward: the slab bytes are its second cost after the MFMAs.
-// ROPE: q and k are rotated while staged, dk is rotated back before its store (dq in the reduce).
-template <int D, int ROPE>
+// ROT_BACK (RoPE): q and k arrive rotated (the caller's rope_qk pre-pass); dk is rotated back before
+// its store here and dq in the reduce, so the gradients are those of the unrotated tensors.
+template <int D, bool ROT_BACK>
 __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_bwd_kernel(AttnBwdArgs a) {
   using C = BwdCfg<D>;
   using I = Img<D>;
@@ -507,7 +454,7 @@ __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_
     for (int ks = 0; ks < NKS; ++ks)
       vf[kh][ks] = key < a.S ? as_frag(ld16(vp + (int64_t)key * a.v_st + 16 * ks + 8 * hh)) : zero_frag();
   }
-  // whole (rotated) K block into LDS for the S and dQ products; a thread stages both RoPE partners
+  // whole K block into LDS for the S and dQ products; a thread stages a row's chunks c and c + CPR / 2
   constexpr int CPR2 = CPR / 2;
 #pragma unroll
   for (int i = 0; i < (BK * CPR2 + NT - 1) / NT; ++i) {
@@ -517,10 +464,6 @@ __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_
       if (kk < a.S) {
         lo = ld16(kp + (int64_t)kk * a.k_st + col * 8);
         hi = ld16(kp + (int64_t)kk * a.k_st + (col + CPR2) * 8);
-        if (ROPE == 1) {
-          const int64_t tab = (int64_t)kk * (D / 2) + col * 8;
-          rope8(lo, hi, a.rope_cos + tab, a.rope_sin + tab, 1.f);
-        }
       }
       I::st_pair(Kl, row, col, lo, hi);
     }
@@ -528,7 +471,7 @@ __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_
 
   vm_wait_all();  // V fragments and the K image ready before the query loop (see common.h)
   __syncthreads();
-  // K fragments of the lane's key rows from the (rotated) image: rows w*32*KH + 32 kh + r,
+  // K fragments of the lane's key rows from the image: rows w*32*KH + 32 kh + r,
   // the Q-fragment read pattern (fq below)
 #pragma unroll
   for (int kh = 0; kh < KH; ++kh)
@@ -551,15 +494,16 @@ __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_
   const int per_head = nqb - qb_start;
   const int total = per_head * G;
 
-  // Q / dO tile chunks: as in the forward, chunk i of a thread is row c / CPR2, column chunk
-  // (c % CPR2) + (i odd ? CPR2 : 0), c = tid + NT * (i / 2): both RoPE partners in one thread
+  // register-staged Q / dO tile chunks (!QDMA): chunk i of a thread is row c / CPR2, column chunk
+  // (c % CPR2) + (i odd ? CPR2 : 0), c = tid + NT * (i / 2), the pairs that Img::st_pair stores
   constexpr int QPAIR = (BQ * CPR2 + NT - 1) / NT;
-  // QDMA (no in-kernel RoPE): the Q / dO tiles go HBM/L2 -> LDS by buffer_load ... lds, issued
+  // QDMA: the Q / dO tiles go HBM/L2 -> LDS by buffer_load ... lds, issued
   // right after the sub-block phase (the dQ task reads neither image) and waited at the next
   // iteration's top: no staging registers, no ds_write pass, one barrier less per iteration.
   // Pieces of 1 KiB = QRP rows; lane l fills row blk * QRP + l / CPR at chunk position l % CPR,
   // which holds logical chunk (l % CPR) ^ I::f(row) (the image's swizzle, applied to the source)
-  constexpr bool QDMA = ROPE == 0;
+  // (the rotate-back instantiations still stage through registers; moving them here is a speed change)
+  constexpr bool QDMA = !ROT_BACK;
   constexpr int QRP = 512 / D, QNP = BQ / QRP, QPPW = 2 * QNP / C::NW;
   static_assert(2 * QNP % C::NW == 0, "Q/dO pieces per wave");
   u32x4 qr[QDMA ? 1 : 2 * QPAIR], dor[QDMA ? 1 : 2 * QPAIR];
@@ -729,10 +673,6 @@ __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_
     for (int i = 0; i < (QDMA ? 0 : 2 * QPAIR); i += 2) {
       const int c = tid + NT * (i / 2), row = c / CPR2, col = c % CPR2;
       if (c < BQ * CPR2) {
-        if (ROPE == 1 && q0 + row < a.T) {
-          const int64_t tab = (int64_t)(q0 + row + off) * (D / 2) + col * 8;
-          rope8(qr[i], qr[i + 1], a.rope_cos + tab, a.rope_sin + tab, 1.f);
-        }
         I::st_pair(Ql, row, col, qr[i], qr[i + 1]);
         I::st_pair(Ol, row, col, dor[i], dor[i + 1]);
       }
@@ -967,7 +907,7 @@ __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_
   for (int kh = 0; kh < KH; ++kh) {
     const int key = kw0 + 32 * kh + r;
     if (key >= a.S) continue;
-    if (ROPE != 0) {
+    if (ROT_BACK) {
       const float* cr = a.rope_cos + (int64_t)key * (D / 2);
       const float* sr = a.rope_sin + (int64_t)key * (D / 2);
       if constexpr (NDB >= 2) {
@@ -1021,7 +961,7 @@ struct RsCfg {
   static constexpr int LDS_ELEMS = BK * D + 2 * BQ * D + BK * BQ;  // bf16: K, Q, dO, dS^T images
 };
 
-template <int D, int ROPE>
+template <int D, bool ROT_BACK>
 __global__ __launch_bounds__(512, 1) void attn_bwd_rs_kernel(AttnBwdArgs a) {
   using C = RsCfg<D>;
   using I = Img<D>;
@@ -1053,7 +993,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_rs_kernel(AttnBwdArgs a) {
   const uint16_t* vp = a.v + b * a.v_sb + (int64_t)hk * a.v_sh;
 
   // this lane's key row of V (wave B) as B-operand fragments; wave A reads its K fragments back
-  // from the (rotated) K image below, so K crosses HBM / L2 once per workgroup
+  // from the K image below, so K crosses HBM / L2 once per workgroup
   bf16x8 kvf[NKS];
   if (!roleA) {
     const int key = kw0 + r;
@@ -1061,7 +1001,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_rs_kernel(AttnBwdArgs a) {
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) kvf[ks] = key < a.S ? as_frag(ld16(src + 16 * ks + 8 * hh)) : zero_frag();
   }
-  // whole (rotated) K block into LDS for the S (wave A) and dQ products
+  // whole K block into LDS for the S (wave A) and dQ products
   constexpr int CPR2 = CPR / 2;
 #pragma unroll
   for (int i = 0; i < (BK * CPR2 + NT - 1) / NT; ++i) {
@@ -1071,10 +1011,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_rs_kernel(AttnBwdArgs a) {
       if (kk < a.S) {
         lo = ld16(kp + (int64_t)kk * a.k_st + col * 8);
         hi = ld16(kp + (int64_t)kk * a.k_st + (col + CPR2) * 8);
-        if (ROPE == 1) {
-          const int64_t tab = (int64_t)kk * (D / 2) + col * 8;
-          rope8(lo, hi, a.rope_cos + tab, a.rope_sin + tab, 1.f);
-        }
       }
       I::st_pair(Kl, row, col, lo, hi);
     }
@@ -1166,10 +1102,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_rs_kernel(AttnBwdArgs a) {
     for (int i = 0; i < 2 * QPAIR; i += 2) {
       const int c = tid + NT * (i / 2), row = c / CPR2, col = c % CPR2;
       if (c < BQ * CPR2) {
-        if (ROPE == 1 && q0 + row < a.T) {
-          const int64_t tab = (int64_t)(q0 + row + off) * (D / 2) + col * 8;
-          rope8(qr[i], qr[i + 1], a.rope_cos + tab, a.rope_sin + tab, 1.f);
-        }
         I::st_pair(Ql, row, col, qr[i], qr[i + 1]);
         I::st_pair(Ol, row, col, dor[i], dor[i + 1]);
       }
@@ -1333,7 +1265,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_rs_kernel(AttnBwdArgs a) {
   // dV (wave A) / dK scaled and rotated back (wave B) for this lane's key
   const int key = kw0 + r;
   if (key >= a.S) return;
-  if (!roleA && ROPE != 0) {
+  if (!roleA && ROT_BACK) {
     const float* cr = a.rope_cos + (int64_t)key * (D / 2);
     const float* sr = a.rope_sin + (int64_t)key * (D / 2);
 #pragma unroll
@@ -1359,8 +1291,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_rs_kernel(AttnBwdArgs a) {
 // l%32 and head dims blk*32 + acc_row(i, l/32), i < 16), sums them in key-block order
 // (deterministic) into the fp32 running sum (kept in the same fragment order) or, on the last
 // pass, transposes the tile through LDS and writes dq = scale * total as whole 16-B row chunks,
-// rotated back with RoPE (each thread holds a dim chunk and its d + D/2 partner).
-template <int D, int BK, int ROPE>
+// rotated back (ROT_BACK: RoPE, each thread holds a dim chunk and its d + D/2 partner).
+template <int D, int BK, bool ROT_BACK>
 __global__ __launch_bounds__(256) void attn_dq_reduce_frag_kernel(AttnBwdArgs a) {
   constexpr int NDB = D / 32, NTH = 64 * NDB, LD = D + 4;  // LD: padded fp32 row of the LDS tile
   __shared__ float tile[32 * LD];
@@ -1435,7 +1367,7 @@ __global__ __launch_bounds__(256) void attn_dq_reduce_frag_kernel(AttnBwdArgs a)
       lo[e] = tile[row * LD + 8 * c + e];
       hi[e] = tile[row * LD + D / 2 + 8 * c + e];
     }
-    if (ROPE != 0) {  // R^T: (x, y) at dims (d, d + D/2) -> (x c + y s, y c - x s)
+    if (ROT_BACK) {  // R^T: (x, y) at dims (d, d + D/2) -> (x c + y s, y c - x s)
       const int64_t tab = (int64_t)(qq + a.S - a.T) * (D / 2) + 8 * c;
       const f32x4* cp = reinterpret_cast<const f32x4*>(a.rope_cos + tab);
       const f32x4* sp = reinterpret_cast<const f32x4*>(a.rope_sin + tab);
@@ -1477,42 +1409,11 @@ int attn_bwd_key_block(int D) {
   if (attn_bwd_ks(D)) return attn_bwd_ks_key_block();
   return D == 128 ? RsCfg<128>::BK : BwdCfg<64>::BK;
 }
-bool attn_bwd_uses_ks(int D) { return attn_bwd_ks(D); }
 
 template <int D>
 static void attn_fwd_t(const AttnFwdArgs& a, hipStream_t st) {
   const int nqb = (a.T + FwdCfg<D>::BM - 1) / FwdCfg<D>::BM;
-  const dim3 grid(nqb * a.B * a.H), blk(64 * FwdCfg<D>::NW);
-  if (a.rope_cos) hipLaunchKernelGGL((attn_fwd_kernel<D, true>), grid, blk, 0, st, a);
-  else hipLaunchKernelGGL((attn_fwd_kernel<D, false>), grid, blk, 0, st, a);
-}
-
-template <int D, int ROPE>
-static void attn_bwd_t(AttnBwdArgs a, hipStream_t st) {
-  const int64_t nrows = (int64_t)a.B * a.T * a.H;
-  const int pre_grid = (int)((nrows * (D / 8) + 255) / 256);
-  const int nkb = (a.S + BwdCfg<D>::BK - 1) / BwdCfg<D>::BK;
-  if (!a.delta_ready) hipLaunchKernelGGL(attn_bwd_pre_kernel<D>, dim3(pre_grid), dim3(256), 0, st, a);
-  // key blocks in passes of at most a.nkb_pass (bounded slab workspace)
-  const int per = a.nkb_pass;
-  for (int kb0 = 0; kb0 < nkb; kb0 += per) {
-    a.kb0 = kb0;
-    a.nkb_pass = min(per, nkb - kb0);
-    hipLaunchKernelGGL((attn_bwd_kernel<D, ROPE>), dim3(a.nkb_pass * a.B * a.Hkv), dim3(BwdCfg<D>::NT), 0, st,
-                       a);
-    hipLaunchKernelGGL((attn_dq_reduce_frag_kernel<D, BwdCfg<D>::BK, ROPE>), dim3(a.B * a.H * a.nqt),
-                       dim3(64 * (D / 32)), 0, st, a);
-    a.nkb_pass = per;
-  }
-}
-
-// RoPE mode: 0 none, 1 rotate q / k inputs and dq / dk outputs, 2 inputs already rotated (the
-// caller's pre-pass), rotate the outputs back only
-template <int D>
-static void attn_bwd_r(const AttnBwdArgs& a, hipStream_t st) {
-  if (!a.rope_cos) attn_bwd_t<D, 0>(a, st);
-  else if (a.rope_in) attn_bwd_t<D, 1>(a, st);
-  else attn_bwd_t<D, 2>(a, st);
+  hipLaunchKernelGGL(attn_fwd_kernel<D>, dim3(nqb * a.B * a.H), dim3(64 * FwdCfg<D>::NW), 0, st, a);
 }
 
 void attn_fwd(const AttnFwdArgs& a, hipStream_t st) {
@@ -1521,65 +1422,56 @@ void attn_fwd(const AttnFwdArgs& a, hipStream_t st) {
   else attn_fwd_t<128>(a, st);
 }
 
-template <int D, int ROPE>
-static void attn_bwd_rs_t(AttnBwdArgs a, hipStream_t st) {
-  using C = RsCfg<D>;
+using BwdKernel = void (*)(AttnBwdArgs);
+
+// One backward over key blocks of BK keys: the delta = rowsum(dO O) pre-pass (skipped when the caller
+// already holds delta), then the key blocks in passes of at most a.nkb_pass (bounded slab workspace);
+// per pass launch_main(a, st) runs the family's main kernel on key blocks [a.kb0, a.kb0 + a.nkb_pass)
+// and the ordered reduce sums their dQ slabs (rotating dq back when RoPE tables are given).
+template <int D, int BK, typename LaunchMain>
+static void attn_bwd_passes(AttnBwdArgs a, hipStream_t st, LaunchMain launch_main) {
   const int64_t nrows = (int64_t)a.B * a.T * a.H;
   const int pre_grid = (int)((nrows * (D / 8) + 255) / 256);
-  const int nkb = (a.S + C::BK - 1) / C::BK;
+  const int nkb = (a.S + BK - 1) / BK;
   const int red_grid = a.B * a.H * a.nqt;  // one workgroup per 32-query tile
+  const BwdKernel reduce =
+      a.rope_cos ? attn_dq_reduce_frag_kernel<D, BK, true> : attn_dq_reduce_frag_kernel<D, BK, false>;
   if (!a.delta_ready) hipLaunchKernelGGL(attn_bwd_pre_kernel<D>, dim3(pre_grid), dim3(256), 0, st, a);
   const int per = a.nkb_pass;
   for (int kb0 = 0; kb0 < nkb; kb0 += per) {
     a.kb0 = kb0;
     a.nkb_pass = min(per, nkb - kb0);
-    hipLaunchKernelGGL((attn_bwd_rs_kernel<D, ROPE>), dim3(a.nkb_pass * a.B * a.Hkv), dim3(C::NT), 0, st, a);
-    hipLaunchKernelGGL((attn_dq_reduce_frag_kernel<D, C::BK, ROPE>), dim3(red_grid), dim3(64 * (D / 32)), 0, st, a);
-    a.nkb_pass = per;
+    launch_main(a, st);
+    hipLaunchKernelGGL(reduce, dim3(red_grid), dim3(64 * (D / 32)), 0, st, a);
   }
 }
 
-template <int D>
-static void attn_bwd_rs_r(const AttnBwdArgs& a, hipStream_t st) {
-  if (!a.rope_cos) attn_bwd_rs_t<D, 0>(a, st);
-  else if (a.rope_in) attn_bwd_rs_t<D, 1>(a, st);
-  else attn_bwd_rs_t<D, 2>(a, st);
+// launch_main of a main-kernel family of this file: one workgroup of nthreads per (key block of the
+// pass, batch, kv-head); the rotate-back instantiation when RoPE tables are given
+static auto bwd_main(BwdKernel plain, BwdKernel rot_back, int nthreads) {
+  return [=](const AttnBwdArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(a.rope_cos ? rot_back : plain, dim3(a.nkb_pass * a.B * a.Hkv), dim3(nthreads), 0, st, a);
+  };
 }
 
-// key-stationary backward (attn_bwd_ks.hip): per pass of key blocks the main kernel (delta formed
-// inside it) and the ordered slab reduce
-template <int D>
-static void attn_bwd_ks_t(AttnBwdArgs a, hipStream_t st) {
-  const int64_t nrows = (int64_t)a.B * a.T * a.H;
-  const int pre_grid = (int)((nrows * (D / 8) + 255) / 256);
-  const int BK = attn_bwd_ks_key_block();
-  const int nkb = (a.S + BK - 1) / BK;
-  const int red_grid = a.B * a.H * a.nqt;  // one workgroup per 32-query tile
-  // delta = rowsum(dO O) pre-pass (skipped when the caller already holds it)
-  if (!a.delta_ready)
-    hipLaunchKernelGGL(attn_bwd_pre_kernel<D>, dim3(pre_grid), dim3(256), 0, st, a);
-  const int per = a.nkb_pass;
-  for (int kb0 = 0; kb0 < nkb; kb0 += per) {
-    a.kb0 = kb0;
-    a.nkb_pass = min(per, nkb - kb0);
-    attn_bwd_ks_launch(a, st);
-    if (a.rope_cos) hipLaunchKernelGGL((attn_dq_reduce_frag_kernel<D, 256, 2>), dim3(red_grid), dim3(64 * (D / 32)), 0, st, a);
-    else hipLaunchKernelGGL((attn_dq_reduce_frag_kernel<D, 256, 0>), dim3(red_grid), dim3(64 * (D / 32)), 0, st, a);
-    a.nkb_pass = per;
-  }
-}
-
-// D = 32 / 64: fused-role kernel; D = 128: role-split kernel; the key-stationary kernel where
-// attn_bwd_ks(D) (q / k pre-rotated: the binding rotates them first when rope_in is set)
+// D = 32 / 64: fused-role kernel; D = 128: role-split kernel; the key-stationary kernel
+// (attn_bwd_ks.hip) where attn_bwd_ks(D).  With RoPE tables q / k arrive rotated and every kernel
+// rotates dq / dk back while storing them.
 void attn_bwd(const AttnBwdArgs& a, hipStream_t st) {
-  if (attn_bwd_ks(a.D) && !(a.rope_cos && a.rope_in)) {
-    if (a.D == 64) attn_bwd_ks_t<64>(a, st);
-    else attn_bwd_ks_t<128>(a, st);
-    return;
+  constexpr int KS_BK = 256;  // attn_bwd_ks_key_block()
+  if (attn_bwd_ks(a.D)) {
+    if (a.D == 64) attn_bwd_passes<64, KS_BK>(a, st, attn_bwd_ks_launch);
+    else attn_bwd_passes<128, KS_BK>(a, st, attn_bwd_ks_launch);
+  } else if (a.D == 32) {
+    attn_bwd_passes<32, BwdCfg<32>::BK>(
+        a, st, bwd_main(attn_bwd_kernel<32, false>, attn_bwd_kernel<32, true>, BwdCfg<32>::NT));
+  } else if (a.D == 64) {
+    attn_bwd_passes<64, BwdCfg<64>::BK>(
+        a, st, bwd_main(attn_bwd_kernel<64, false>, attn_bwd_kernel<64, true>, BwdCfg<64>::NT));
+  } else {
+    attn_bwd_passes<128, RsCfg<128>::BK>(
+        a, st, bwd_main(attn_bwd_rs_kernel<128, false>, attn_bwd_rs_kernel<128, true>, RsCfg<128>::NT));
   }
-  if (a.D == 32) attn_bwd_r<32>(a, st);
-  else if (a.D == 64) attn_bwd_r<64>(a, st);
-  else attn_bwd_rs_r<128>(a, st);
 }
 
 }  // namespace pllm

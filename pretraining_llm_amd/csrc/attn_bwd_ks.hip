@@ -77,9 +77,9 @@ struct ImgT {
   static PL_DEV int off(int r, int col) { return r * W + (((col >> 3) ^ f(r)) << 3) + (col & 7); }
 };
 
-template <int D, int ROPE>
+// ROT_BACK (RoPE): q / k arrive rotated, dk is rotated back before its store (dq in the reduce)
+template <int D, bool ROT_BACK>
 __global__ __launch_bounds__(256, 1) void attn_bwd_ks_kernel(AttnBwdArgs a) {
-  static_assert(ROPE != 1, "KS backward: q / k pre-rotated (ROPE 0 or 2)");
   using C = KsCfg<D>;
   using I = Img<D>;
   using IT = ImgT<C::BQ>;
@@ -493,7 +493,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_ks_kernel(AttnBwdArgs a) {
   for (int kh = 0; kh < 2; ++kh) {
     const int key = kw0 + 32 * kh + r;
     if (key >= a.S) continue;
-    if (ROPE != 0) {
+    if (ROT_BACK) {
       const float* cr = a.rope_cos + (int64_t)key * (D / 2);
       const float* sr = a.rope_sin + (int64_t)key * (D / 2);
 #pragma unroll
@@ -524,11 +524,11 @@ int attn_bwd_ks_key_block() { return KsCfg<128>::BK; }
 void attn_bwd_ks_launch(const AttnBwdArgs& a, hipStream_t st) {
   const dim3 grid(a.nkb_pass * a.B * a.Hkv), blk(256);
   if (a.D == 64) {
-    if (a.rope_cos) hipLaunchKernelGGL((attn_bwd_ks_kernel<64, 2>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((attn_bwd_ks_kernel<64, 0>), grid, blk, 0, st, a);
+    if (a.rope_cos) hipLaunchKernelGGL((attn_bwd_ks_kernel<64, true>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((attn_bwd_ks_kernel<64, false>), grid, blk, 0, st, a);
   } else {
-    if (a.rope_cos) hipLaunchKernelGGL((attn_bwd_ks_kernel<128, 2>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((attn_bwd_ks_kernel<128, 0>), grid, blk, 0, st, a);
+    if (a.rope_cos) hipLaunchKernelGGL((attn_bwd_ks_kernel<128, true>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((attn_bwd_ks_kernel<128, false>), grid, blk, 0, st, a);
   }
 }
 

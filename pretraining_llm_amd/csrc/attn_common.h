@@ -1,5 +1,5 @@
 // Shared device helpers of the attention kernels (attention.hip, attn_bwd_ks.hip): MFMA / transposed-read
-// wrappers, accumulator layout, RoPE rotation, the row-per-lane epilogue store and the swizzled LDS
+// wrappers, accumulator layout, the row-per-lane epilogue store and the swizzled LDS
 // images.  Header-only, internal linkage (each translation unit gets its own copy).
 #pragma once
 #include "common.h"
@@ -33,37 +33,6 @@ PL_DEV bf16x8 pack_frag(const f32x16& x, int s) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) f[j] = (bf16)x[8 * s + j];
   return f;
-}
-
-// ---------------------------------------------------------------------------
-// Fused RoPE (rotate-half convention, ops/reference.py rope): element i < D/2 of a head row
-// pairs with i + D/2; a' = a cos - b sin, b' = b cos + a sin at the row's position.  The kernels
-// rotate q and k while staging them (registers / LDS images) and un-rotate dq and dk before
-// the final stores, so the packed QKV tensor and its gradient stay unrotated and no separate
-// RoPE pass over [B, T, H, D] exists in forward or backward.
-// Rotates 8 + 8 bf16 values (a = elements i0..i0+7, b = i0+D/2..) held as two 16-B chunks.
-PL_DEV void rope8(u32x4& lo, u32x4& hi, const float* cosr, const float* sinr, float dir) {
-  float a[8], b[8], c[8], sn[8];
-  unpack8(lo, a);
-  unpack8(hi, b);
-  const f32x4* cp = reinterpret_cast<const f32x4*>(cosr);
-  const f32x4* sp = reinterpret_cast<const f32x4*>(sinr);
-  const f32x4 c0 = cp[0], c1 = cp[1], s0 = sp[0], s1 = sp[1];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    c[e] = c0[e];
-    c[4 + e] = c1[e];
-    sn[e] = s0[e] * dir;
-    sn[4 + e] = s1[e] * dir;
-  }
-  float o1[8], o2[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    o1[e] = a[e] * c[e] - b[e] * sn[e];
-    o2[e] = b[e] * c[e] + a[e] * sn[e];
-  }
-  lo = pack8(o1);
-  hi = pack8(o2);
 }
 
 // Row-per-lane epilogue of 32x32 accumulator tiles (guide T21): acc[db] holds, for the lane's
@@ -114,7 +83,7 @@ struct Img {
   }
   // element offset of (row, col); col's 8-aligned chunk is swizzled, col&7 kept
   static PL_DEV int off(int r, int col) { return r * W + (((col >> 3) ^ f(r)) << 3) + (col & 7); }
-  // a row's two RoPE-partner halves (chunks c and c + W/16) stored so that every 8-lane group
+  // a row's two halves (chunks c and c + W/16, one thread of the register-staged paths) stored so that every 8-lane group
   // of ds_write_b128 (bank = byte address mod 128) covers 128 distinct bytes: at W = 64 rows 2k
   // and 2k+1 share f, so an odd row stores its upper half first (same image, same reads)
   static PL_DEV void st_pair(uint16_t* base, int r, int c, const u32x4& lo, const u32x4& hi) {

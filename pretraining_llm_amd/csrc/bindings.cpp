@@ -826,7 +826,7 @@ void check_rows_span(const Tensor& t, const char* name) {
               " spans >= 2 GiB within one head (sequence x row stride too large for 32-bit offsets)");
 }
 
-// fused RoPE tables: fp32 contiguous [>= S, D/2] on the device (both or neither)
+// RoPE tables of the attention backward: fp32 contiguous [>= S, D/2] on the device (both or neither)
 void check_rope(const std::optional<Tensor>& c, const std::optional<Tensor>& sn, int64_t S, int64_t D) {
   TORCH_CHECK(c.has_value() == sn.has_value(), "attention: rope_cos and rope_sin go together");
   if (!c) return;
@@ -838,8 +838,7 @@ void check_rope(const std::optional<Tensor>& c, const std::optional<Tensor>& sn,
   }
 }
 
-std::vector<Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, bool causal, double scale,
-                             const std::optional<Tensor>& rope_cos, const std::optional<Tensor>& rope_sin) {
+std::vector<Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, bool causal, double scale) {
   const int64_t D = q.size(3);
   TORCH_CHECK(pllm::attn_supported_head_dim((int)D), "attention: head dim must be 32, 64 or 128, got ", D);
   check_head_view(q, "q", D);
@@ -849,7 +848,6 @@ std::vector<Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, 
   TORCH_CHECK(k.size(0) == B && v.size(0) == B && v.size(1) == S && v.size(2) == Hkv, "k/v shape");
   TORCH_CHECK(H % Hkv == 0, "H % Hkv");
   TORCH_CHECK(!causal || S >= T, "causal attention needs S >= T");
-  check_rope(rope_cos, rope_sin, S, D);
   check_rows_span(k, "k");
   check_rows_span(v, "v");
   Tensor o = at::empty({B, T, H, D}, q.options());
@@ -860,8 +858,6 @@ std::vector<Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, 
   a.v = (const uint16_t*)v.data_ptr();
   a.o = (uint16_t*)o.data_ptr();
   a.lse = lse.data_ptr<float>();
-  a.rope_cos = rope_cos ? rope_cos->data_ptr<float>() : nullptr;
-  a.rope_sin = rope_sin ? rope_sin->data_ptr<float>() : nullptr;
   a.B = B; a.H = H; a.Hkv = Hkv; a.T = T; a.S = S; a.D = D;
   a.q_sb = q.stride(0); a.q_st = q.stride(1); a.q_sh = q.stride(2);
   a.k_sb = k.stride(0); a.k_st = k.stride(1); a.k_sh = k.stride(2);
@@ -948,10 +944,12 @@ int64_t attn_bwd_ws_bytes() {
   return g_attn_ws_bytes;
 }
 
-// dq/dk/dv are written into caller-provided views (e.g. slices of a packed dQKV buffer)
+// dq/dk/dv are written into caller-provided views (e.g. slices of a packed dQKV buffer).  With RoPE
+// tables q / k are the rotated heads (rope / rope_qk; query t at position t + S - T) and dq / dk come
+// back rotated back, i.e. as the gradients of the unrotated heads
 void attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o, const Tensor& lse,
               Tensor& dq, Tensor& dk, Tensor& dv, bool causal, double scale, const std::optional<Tensor>& rope_cos,
-              const std::optional<Tensor>& rope_sin, bool rope_in, const std::optional<Tensor>& delta_in) {
+              const std::optional<Tensor>& rope_sin, const std::optional<Tensor>& delta_in) {
   const int64_t D = q.size(3);
   TORCH_CHECK(pllm::attn_supported_head_dim((int)D), "attention: head dim must be 32, 64 or 128");
   for (auto& pr : std::vector<std::pair<const Tensor*, const char*>>{
@@ -984,26 +982,9 @@ void attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor
   const int64_t per = std::max<int64_t>(1, std::min<int64_t>(nkb, ws_budget / std::max<int64_t>(1, slab_bytes)));
   Tensor dq_acc = at::empty({per, slab_elems}, q.options());  // bf16 partial slabs
   Tensor dq_sum = per < nkb ? at::empty({slab_elems}, q.options().dtype(at::kFloat)) : Tensor();
-  // the key-stationary backward stages q / k by LDS DMA: with in-kernel RoPE requested, rotate them
-  // here once (positions t + S - T for queries, s for keys) and run it on the rotated copies
-  Tensor qrot, krot;
-  const bool ks_rot = rope_cos && rope_in && pllm::attn_bwd_uses_ks((int)D);
-  if (ks_rot) {
-    const Tensor qc = q.contiguous(), kc = k.contiguous();
-    qrot = at::empty_like(qc);
-    krot = at::empty_like(kc);
-    if (B * T > 0)
-      pllm::rope(qc.data_ptr(), qrot.data_ptr(), rope_cos->data_ptr<float>(), rope_sin->data_ptr<float>(), B * T,
-                 (int)T, (int)H, (int)H, (int)D, (int)(S - T), false, cur_stream());
-    if (B * S > 0)
-      pllm::rope(kc.data_ptr(), krot.data_ptr(), rope_cos->data_ptr<float>(), rope_sin->data_ptr<float>(), B * S,
-                 (int)S, (int)Hkv, (int)Hkv, (int)D, 0, false, cur_stream());
-  }
-  const Tensor& qx = ks_rot ? qrot : q;
-  const Tensor& kx = ks_rot ? krot : k;
   AttnBwdArgs a{};
-  a.q = (const uint16_t*)qx.data_ptr();
-  a.k = (const uint16_t*)kx.data_ptr();
+  a.q = (const uint16_t*)q.data_ptr();
+  a.k = (const uint16_t*)k.data_ptr();
   a.v = (const uint16_t*)v.data_ptr();
   a.o = (const uint16_t*)o.data_ptr();
   a.dO = (const uint16_t*)dout.data_ptr();
@@ -1014,7 +995,6 @@ void attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor
   a.dq_acc = (uint16_t*)dq_acc.data_ptr();
   a.dq_sum = dq_sum.defined() ? dq_sum.data_ptr<float>() : nullptr;
   a.kb0 = 0;
-  a.rope_in = rope_in && !ks_rot ? 1 : 0;
   a.slab = slab_elems;
   a.nqt = (int)nqt;
   a.nkb_pass = (int)per;
@@ -1022,8 +1002,8 @@ void attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor
   a.dk = (uint16_t*)dk.data_ptr();
   a.dv = (uint16_t*)dv.data_ptr();
   a.B = B; a.H = H; a.Hkv = Hkv; a.T = T; a.S = S; a.D = D;
-  a.q_sb = qx.stride(0); a.q_st = qx.stride(1); a.q_sh = qx.stride(2);
-  a.k_sb = kx.stride(0); a.k_st = kx.stride(1); a.k_sh = kx.stride(2);
+  a.q_sb = q.stride(0); a.q_st = q.stride(1); a.q_sh = q.stride(2);
+  a.k_sb = k.stride(0); a.k_st = k.stride(1); a.k_sh = k.stride(2);
   a.v_sb = v.stride(0); a.v_st = v.stride(1); a.v_sh = v.stride(2);
   a.o_sb = o.stride(0); a.o_st = o.stride(1); a.o_sh = o.stride(2);
   a.do_sb = dout.stride(0); a.do_st = dout.stride(1); a.do_sh = dout.stride(2);
@@ -1095,9 +1075,9 @@ TORCH_LIBRARY(pllm, m) {
   m.def("transpose_plan(Tensor[] src, Tensor[] dst) -> Tensor");
   m.def("transpose_run(Tensor desc, int total_tiles) -> ()");
   m.def("sample(Tensor logits, float temperature, int seed) -> Tensor");
-  m.def("attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None) -> Tensor[]");
+  m.def("attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale) -> Tensor[]");
   m.def("attn_decode(Tensor q, Tensor k, Tensor v, float scale, Tensor? seqlen=None) -> Tensor");
-  m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, bool rope_in=True, Tensor? delta=None) -> ()");
+  m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, Tensor? delta=None) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(pllm, CUDA, m) {

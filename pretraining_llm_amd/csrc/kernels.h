@@ -10,9 +10,6 @@ struct AttnFwdArgs {
   const uint16_t *q, *k, *v;
   uint16_t* o;
   float* lse;  // [B, H, T] natural-log LSE, may be null
-  // optional fused RoPE (rotate-half) of q and k: fp32 tables [>= S, D/2]; query row t sits at
-  // position t + S - T, key row j at position j
-  const float *rope_cos, *rope_sin;
   int B, H, Hkv, T, S, D;
   int64_t q_sb, q_st, q_sh, k_sb, k_st, k_sh, v_sb, v_st, v_sh, o_sb, o_st, o_sh;
   float scale, scale_log2;
@@ -35,12 +32,13 @@ struct DecodeArgs {
 struct AttnBwdArgs {
   const uint16_t *q, *k, *v, *o, *dO;
   const float* lse;
-  const float *rope_cos, *rope_sin;  // optional fused RoPE (as AttnFwdArgs); dq/dk un-rotated
+  // optional RoPE (rotate-half) fp32 tables [>= S, D/2]: q / k arrive rotated (query row t at position
+  // t + S - T, key row j at position j) and dq / dk leave un-rotated
+  const float *rope_cos, *rope_sin;
   float* delta;   // [B, H, T] scratch
   uint16_t* dq_acc;  // [nkb_pass][B, T, H, D] bf16 per-key-block dQ partial slabs of one pass
   float* dq_sum;  // [B, T, H, D] fp32 running dQ sum across passes (null when one pass)
   int kb0, nkb_pass;  // first key block of the pass / key blocks per pass (set by the host)
-  int rope_in;        // with rope tables: 1 = rotate q / k in-kernel, 0 = already rotated (outputs only)
   int64_t slab;       // elements per dQ slab (>= B * ceil32(T) * H * D)
   int nqt;            // ceil(T / 32): query tiles per head in the fragment-order slab (RS kernel)
   uint16_t *dq, *dk, *dv;
@@ -204,7 +202,6 @@ void gemv(const GemvArgs& a, hipStream_t st);
 // attention.hip
 bool attn_supported_head_dim(int D);
 int attn_bwd_key_block(int D);  // keys per backward workgroup = dq_acc slab count divisor
-bool attn_bwd_uses_ks(int D);    // the key-stationary backward serves head dim D (q / k must be pre-rotated)
 // attn_bwd_ks.hip: keys per workgroup; one pass of the key-stationary main kernel (AttnBwdArgs as attn_bwd)
 int attn_bwd_ks_key_block();
 

@@ -657,45 +657,59 @@ def _split_qkv(qkv, H, Hkv, D):
     return q, k, v
 
 
+def _qkv_heads(qkv, qk, H, Hkv, D):
+    """q, k, v head views of the packed tensor; q / k from the rotated buffer ``qk`` when there is one."""
+    B, T, _ = qkv.shape
+    q, k, v = _split_qkv(qkv, H, Hkv, D)
+    if qk is not None:
+        q = qk[..., : H * D].view(B, T, H, D)
+        k = qk[..., H * D:].view(B, T, Hkv, D)
+    return q, k, v
+
+
+def _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin):
+    """Forward attention over packed qkv -> (qk, o, lse); ``qk`` is the rotated q / k buffer of the
+    RoPE pre-pass ([B, T, (H + Hkv) D], None without RoPE), which the backward reads again."""
+    T = qkv.shape[1]
+    D = qkv.shape[2] // (H + 2 * Hkv)
+    qk = _ops().rope_qk(qkv, cos, sin, H + 2 * Hkv, H + Hkv, T) if cos is not None else None
+    q, k, v = _qkv_heads(qkv, qk, H, Hkv, D)
+    o, lse = _ops().attn_fwd(q, k, v, causal, scale)
+    return qk, o, lse
+
+
+def _attn_packed_bwd(do, qkv, qk, o, lse, cfg, cos, sin, delta=None):
+    """Backward attention -> packed dqkv (for the unrotated qkv: the kernels rotate dq / dk back).
+    ``do``: [B, T, H, D] contiguous; ``delta``: rowsum(dO * O) when the caller already holds it."""
+    H, Hkv, D, causal, scale = cfg
+    q, k, v = _qkv_heads(qkv, qk, H, Hkv, D)
+    dqkv = torch.empty_like(qkv)
+    dq, dk, dv = _split_qkv(dqkv, H, Hkv, D)
+    _attn_ws(qkv.device)
+    _ops().attn_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, cos, sin, delta)
+    return dqkv
+
+
 class _FlashAttnPacked(torch.autograd.Function):
     """Attention over the packed QKV projection.  With ``cos``/``sin`` (RoPE) one pre-pass
     writes the rotated q and k heads to a [B, T, (H + Hkv) D] buffer that both the forward and
     the backward kernels read (kept for the backward: 2/3 of qkv for MHA); the backward kernels
     rotate dq / dk back while storing them, so the gradient comes back for the unrotated packed
-    tensor.  Rotating inside the tile loops instead (rope_pre=False: tables read per tile)
-    measured +22 % forward / +25 % backward at the llama shape (profiles/r2_rope_prepass_ab.txt)."""
+    tensor.  (Rotating inside the kernels' tile loops instead measured +22 % forward / +25 %
+    backward at the llama shape -- the round-2 RoPE A/B record under profiles/ -- and was removed.)"""
 
     @staticmethod
     def forward(ctx, qkv, H, Hkv, causal, scale, cos, sin):
         B, T, W = qkv.shape
-        D = W // (H + 2 * Hkv)
-        q, k, v = _split_qkv(qkv, H, Hkv, D)
-        qk = None
-        if cos is not None and _ROPE_PREPASS:
-            qk = _ops().rope_qk(qkv, cos, sin, H + 2 * Hkv, H + Hkv, T)
-            q = qk[..., : H * D].view(B, T, H, D)
-            k = qk[..., H * D:].view(B, T, Hkv, D)
-            o, lse = _ops().attn_fwd(q, k, v, causal, scale)
-        else:
-            o, lse = _ops().attn_fwd(q, k, v, causal, scale, cos, sin)
+        qk, o, lse = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin)
         ctx.save_for_backward(qkv, qk, o, lse, cos, sin)
-        ctx.cfg = (H, Hkv, D, causal, scale)
-        return o.view(B, T, H * D)
+        ctx.cfg = (H, Hkv, W // (H + 2 * Hkv), causal, scale)
+        return o.view(B, T, -1)
 
     @staticmethod
     def backward(ctx, do):
         qkv, qk, o, lse, cos, sin = ctx.saved_tensors
-        H, Hkv, D, causal, scale = ctx.cfg
-        B, T, _ = qkv.shape
-        q, k, v = _split_qkv(qkv, H, Hkv, D)
-        if qk is not None:
-            q = qk[..., : H * D].view(B, T, H, D)
-            k = qk[..., H * D:].view(B, T, Hkv, D)
-        dqkv = torch.empty_like(qkv)
-        dq, dk, dv = _split_qkv(dqkv, H, Hkv, D)
-        _attn_ws(qkv.device)
-        _ops().attn_bwd(do.contiguous().view(B, T, H, D), q, k, v, o, lse, dq, dk, dv, causal, scale, cos, sin,
-                        qk is None)
+        dqkv = _attn_packed_bwd(do.contiguous().view(o.shape), qkv, qk, o, lse, ctx.cfg, cos, sin)
         return dqkv, None, None, None, None, None, None
 
 
@@ -710,15 +724,7 @@ class _AttnProjFn(torch.autograd.Function):
     def forward(ctx, qkv, H, Hkv, causal, scale, cos, sin, w, b, bias_ext, res=None):
         B, T, W = qkv.shape
         D = W // (H + 2 * Hkv)
-        q, k, v = _split_qkv(qkv, H, Hkv, D)
-        qk = None
-        if cos is not None and _ROPE_PREPASS:
-            qk = _ops().rope_qk(qkv, cos, sin, H + 2 * Hkv, H + Hkv, T)
-            q = qk[..., : H * D].view(B, T, H, D)
-            k = qk[..., H * D:].view(B, T, Hkv, D)
-            o, lse = _ops().attn_fwd(q, k, v, causal, scale)
-        else:
-            o, lse = _ops().attn_fwd(q, k, v, causal, scale, cos, sin)
+        qk, o, lse = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin)
         ctx.save_for_backward(qkv, qk, o, lse, cos, sin)
         ctx.cfg = (H, Hkv, D, causal, scale)
         ctx.w, ctx.b, ctx.bias_ext = w, b, bias_ext
@@ -762,15 +768,7 @@ class _AttnProjFn(torch.autograd.Function):
         if wt is None or getattr(w, "_pllm_wT_ver", None) != w._version:
             wt = w.t().contiguous()
         do2, delta = _ops().gemm_tn(dy2, wt, None, 6, o2, None, T)
-        q, k, v = _split_qkv(qkv, H, Hkv, D)
-        if qk is not None:
-            q = qk[..., : H * D].view(B, T, H, D)
-            k = qk[..., H * D:].view(B, T, Hkv, D)
-        dqkv = torch.empty_like(qkv)
-        dq, dk, dv = _split_qkv(dqkv, H, Hkv, D)
-        _attn_ws(qkv.device)
-        _ops().attn_bwd(do2.view(B, T, H, D), q, k, v, o, lse, dq, dk, dv, causal, scale, cos, sin, qk is None,
-                        delta)
+        dqkv = _attn_packed_bwd(do2.view(B, T, H, D), qkv, qk, o, lse, ctx.cfg, cos, sin, delta)
         return dqkv, None, None, None, None, None, None, dw, db, None, (dy if ctx.has_res else None)
 
 
@@ -821,10 +819,6 @@ def _attn_ws(device):
         _ATTN_WS_MB[0] = mb
 
 
-# RoPE for the HIP attention: pre-pass rotation (default) or rotation inside the kernels' tile loops
-_ROPE_PREPASS = _ab("rope_prepass", True)
-
-
 class _RopePackedFn(torch.autograd.Function):
     """Rotate the q and k heads of a packed qkv tensor (rotate-half convention)."""
 
@@ -863,7 +857,7 @@ def attention_packed(qkv, n_head: int, n_kv_head: int, causal: bool = True, scal
     D = W // (n_head + 2 * n_kv_head)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     if _hip_op("attn", qkv):
-        # RoPE fused into the attention kernels (q/k rotated while staged, dq/dk rotated back)
+        # RoPE: one rope_qk pre-pass rotates q / k, the backward kernels rotate dq / dk back
         return _FlashAttnPacked.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin)
     if rope_cos is not None:
         qkv = rope_packed(qkv, rope_cos, rope_sin, n_head, n_kv_head)

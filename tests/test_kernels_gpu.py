@@ -951,7 +951,7 @@ def test_lm_head_ce_chunked(chunk, with_bias, monkeypatch):
                                          (128, 2048, 4, 1, 1), (128, 4096, 2, 2, 1), (64, 1000, 4, 4, 2)])
 def test_attention_bwd_long_sequences(D, T, H, Hkv, B):
     """Backward at the shipped sequence lengths (2048 / 4096, several key blocks and dQ slabs),
-    D = 32 / 64 (fused-role kernel) and 128 (role-split kernel), GQA, ragged T, vs fp32 torch; a
+    D = 32 / 64 (fused-role kernel) and 128 (key-stationary kernel), GQA, ragged T, vs fp32 torch; a
     forced multi-pass run (bounded dQ workspace) is bit-identical to the single-pass one."""
     torch.manual_seed(T + D)
     q = torch.randn(B, T, H, D, device=DEV).bfloat16()
@@ -978,21 +978,10 @@ def test_attention_bwd_long_sequences(D, T, H, Hkv, B):
 
 
 @pytest.mark.parametrize("D,Hkv", [(64, 4), (128, 2), (64, 1), (32, 2)])
-@pytest.mark.parametrize("prepass", [True, False])
-def test_attention_fused_rope_fwd_bwd(D, Hkv, prepass):
+def test_attention_fused_rope_fwd_bwd(D, Hkv):
     """RoPE with the HIP attention == rotate-half RoPE + attention in fp32 torch, gradients
-    w.r.t. the UNROTATED packed qkv: pre-pass (rope_qk once, backward rotates dq/dk back while
-    storing them) and in-kernel rotation (q/k rotated while staged)."""
-    from pretraining_llm_amd import ops
-    old = ops._ROPE_PREPASS
-    ops._ROPE_PREPASS = prepass
-    try:
-        _rope_case(D, Hkv)
-    finally:
-        ops._ROPE_PREPASS = old
-
-
-def _rope_case(D, Hkv):
+    w.r.t. the UNROTATED packed qkv: rope_qk rotates q / k once, the backward rotates dq / dk
+    back while storing them."""
     from pretraining_llm_amd import ops
     from pretraining_llm_amd.ops import reference as ref
     torch.manual_seed(29 + D)
@@ -1185,10 +1174,11 @@ def test_attention_bwd_key_stationary(D, T, S, H, Hkv, B, causal):
 @pytest.mark.parametrize("D", [64, 128])
 @pytest.mark.parametrize("T,S", [(200, 264), (300, 340)])
 def test_attention_bwd_key_stationary_rope_offset(D, T, S):
-    """In-kernel RoPE (rope_in=True) with queries aligned to the END of longer key rows (S > T; offsets 64 and
-    40, the latter not a multiple of 32): the key-stationary backward runs on copies the binding pre-rotates
-    (queries at positions t + S - T, keys at s), then rotates dq / dk back.  Against fp32 rotate-half RoPE +
-    causal attention, gradients w.r.t. the UNROTATED q / k."""
+    """RoPE with queries aligned to the END of longer key rows (S > T; offsets 64 and 40, the latter not a
+    multiple of 32): q is rotated at positions t + S - T and k at s (the rope op), the forward and the
+    backward run on the rotated heads and the backward rotates dq / dk back -- under the key-stationary
+    kernels (mask 3) and under the fused-role D = 64 / role-split D = 128 kernels (mask 0).  Against fp32
+    rotate-half RoPE + causal attention, gradients w.r.t. the UNROTATED q / k."""
     from pretraining_llm_amd import ops
     from pretraining_llm_amd.ops import reference as ref
     torch.manual_seed(T + S + D + 5)
@@ -1204,15 +1194,18 @@ def test_attention_bwd_key_stationary_rope_offset(D, T, S):
     kr = ref.rope(kf, cos[:S], sin[:S])
     of, _ = _attn_ref(qr, kr, vf, True, scale)
     of.backward(do.float())
+    qrot = torch.ops.pllm.rope(q.view(B, T, H * D), cos, sin, H, H, T, S - T, False).view(B, T, H, D)
+    krot = torch.ops.pllm.rope(k.view(B, S, Hkv * D), cos, sin, Hkv, Hkv, S, 0, False).view(B, S, Hkv, D)
+    o, lse = torch.ops.pllm.attn_fwd(qrot, krot, v, True, scale)
+    assert _rel(o, of) < 1.5e-2, _rel(o, of)
     try:
-        torch.ops.pllm.attn_bwd_set_ks(3)  # key-stationary at D = 64 and 128
-        o, lse = torch.ops.pllm.attn_fwd(q, k, v, True, scale, cos, sin)
-        assert _rel(o, of) < 1.5e-2, _rel(o, of)
-        got = [torch.empty_like(t) for t in (q, k, v)]
-        torch.ops.pllm.attn_bwd(do, q, k, v, o, lse, *got, True, scale, cos, sin, True)
-        for a, b, n in zip(got, (qf.grad, kf.grad, vf.grad), ("dq", "dk", "dv")):
-            assert not a.isnan().any(), n
-            assert _rel(a, b) < 3e-2, (n, _rel(a, b))
+        for ks in (3, 0):  # key-stationary at D = 64 and 128 / fused-role D = 64 and role-split D = 128
+            torch.ops.pllm.attn_bwd_set_ks(ks)
+            got = [torch.empty_like(t) for t in (q, k, v)]
+            torch.ops.pllm.attn_bwd(do, qrot, krot, v, o, lse, *got, True, scale, cos, sin)
+            for a, b, n in zip(got, (qf.grad, kf.grad, vf.grad), ("dq", "dk", "dv")):
+                assert not a.isnan().any(), (ks, n)
+                assert _rel(a, b) < 3e-2, (ks, n, _rel(a, b))
     finally:
         torch.ops.pllm.attn_bwd_set_ks(2)  # the shipped default: D = 128 only
 
