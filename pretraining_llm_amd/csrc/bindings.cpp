@@ -1065,6 +1065,7 @@ TORCH_LIBRARY(pllm, m) {
   m.def("scale_(Tensor(a!) x, Tensor s) -> ()");
   m.def("lse_merge_(Tensor(a!) o_acc, Tensor(b!) lse_acc, Tensor o, Tensor lse) -> ()");
   m.def("zero_ranges_(Tensor(a!) buf, Tensor ranges, int total_len) -> ()");
+  m.def("cross_entropy_max_vocab() -> int", []() { return (int64_t)pllm::cross_entropy_max_vocab(); });
   m.def("cross_entropy(Tensor logits, Tensor targets, Tensor(a!)? dlogits, int ignore_index, Tensor? inv_n=None) -> Tensor");
   m.def("adamw_(Tensor(a!) param, Tensor(b!) master, Tensor(c!) m, Tensor(d!) v, Tensor grad, float lr, float b1, float b2, float eps, float wd, int step, float grad_scale, Tensor? scale, Tensor? wd_mask, Tensor? hyper=None) -> ()");
   m.def("sumsq(Tensor x) -> Tensor");

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(const uint16_t* __restri
   // pass instead of being stored (VALU is idle in this HBM-bound kernel).
   constexpr float LOG2E = 1.4426950408889634f;
   constexpr int CE_WAVES = CE_THREADS / 64;
-  __shared__ float scratch[2 * CE_WAVES];
+  __shared__ float scratch[3 * CE_WAVES];
   const int row = blockIdx.x;
   const uint16_t* x = logits + (size_t)row * ld;
   const int nch = V >> 3;
@@ -72,7 +72,15 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(const uint16_t* __restri
     // the lane's own max, its exp-sum against it, then ONE block reduction of (max, sum) pairs
     // (2 barriers instead of 4; the target logit is read before any lane can overwrite it)
     const float xt = (threadIdx.x == 0 && valid) ? bf2f(x[t]) : 0.f;
-    const float ml = m == -INFINITY ? 0.f : m * LOG2E;
+    // ms: the lane's maximum times log2(e), rounded ONCE.  Every exp-sum is taken against such a rounded value,
+    // so rebasing a sum from one maximum to another multiplies it by 2^(difference of two of them).  The merges
+    // carry ms itself (its maximum is the scaled maximum): written `m * LOG2E - c`, the compiler contracts the
+    // rebase into fma(m, LOG2E, -c), which is off by the product's rounding residual (up to 2^-18 at |m| = 80)
+    // even for m's own c -- seven merges per row inflated the sum, and at a confident target softmax - 1 came
+    // out as 1e-5 instead of 0.  The empty asm keeps the product from being folded into a later subtraction.
+    float ms = m * LOG2E;
+    asm volatile("" : "+v"(ms));
+    const float ml = m == -INFINITY ? 0.f : ms;
 #pragma unroll
     for (int k = 0; k < CH; ++k) asm volatile("" : "+v"(v[k]));
     float sl = 0.f;
@@ -84,31 +92,37 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(const uint16_t* __restri
       for (int j = 0; j < 8; ++j) sl += fast_exp2(__builtin_fmaf(f[j], LOG2E, -ml));
     }
     if (tj < V) sl += fast_exp2(__builtin_fmaf(tv, LOG2E, -ml));
-    // wave: pairwise (m, s) merge, then across waves through LDS
+    // wave: pairwise (scaled max, sum) merge, then across waves through LDS
+    const float ms0 = ms;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-      const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(sl, o, 64);
-      const float mn = fmaxf(m, m2);
-      const float mnl = mn == -INFINITY ? 0.f : mn * LOG2E;
-      sl = (m == -INFINITY ? 0.f : sl * fast_exp2(m * LOG2E - mnl)) +
-           (m2 == -INFINITY ? 0.f : s2 * fast_exp2(m2 * LOG2E - mnl));
-      m = mn;
+      const float m2 = __shfl_xor(ms, o, 64), s2 = __shfl_xor(sl, o, 64);
+      const float mn = fmaxf(ms, m2);
+      sl = (ms == -INFINITY ? 0.f : sl * fast_exp2(ms - mn)) + (m2 == -INFINITY ? 0.f : s2 * fast_exp2(m2 - mn));
+      ms = mn;
     }
+    // the plain maximum (for the loss) from a lane that holds it: the rounded product is monotone in m
+    // (and distinct for distinct bf16 values)
+    m = __shfl(m, __ffsll((unsigned long long)__ballot(ms0 == ms)) - 1, 64);
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
     if (l == 0) {
       scratch[w] = m;
       scratch[CE_WAVES + w] = sl;
+      scratch[2 * CE_WAVES + w] = ms;
     }
     __syncthreads();
     float mb = -INFINITY;
+    mc = -INFINITY;
 #pragma unroll
-    for (int i = 0; i < CE_WAVES; ++i) mb = fmaxf(mb, scratch[i]);
-    mc = mb * LOG2E;
+    for (int i = 0; i < CE_WAVES; ++i) {
+      mb = fmaxf(mb, scratch[i]);
+      mc = fmaxf(mc, scratch[2 * CE_WAVES + i]);
+    }
     float sb = 0.f;
 #pragma unroll
     for (int i = 0; i < CE_WAVES; ++i) {
-      const float mi = scratch[i];
-      if (mi != -INFINITY) sb += scratch[CE_WAVES + i] * fast_exp2(mi * LOG2E - mc);
+      const float mi = scratch[2 * CE_WAVES + i];
+      if (mi != -INFINITY) sb += scratch[CE_WAVES + i] * fast_exp2(mi - mc);
     }
     m = mb;
     s = sb;
@@ -180,6 +194,9 @@ void cross_entropy(const void* logits, int64_t ld, const int64_t* targets, int N
   else ce_launch<CE_THREADS, false>(logits, ld, targets, N, V, ignore_index, loss, dlogits, inv_n, st);
 }
 
-int cross_entropy_max_vocab() { return CE_THREADS * 8 * 32 + CE_THREADS; }
+// 32 chunks of 8 logits per lane.  The op takes V % 8 == 0 only, so the kernel's scalar tail never adds to that:
+// with a "+ CE_THREADS" allowance here, V = 131080 .. 131584 were accepted, ran as CH = 32, and the vectors past
+// 131072 were neither read nor written.
+int cross_entropy_max_vocab() { return CE_THREADS * 8 * 32; }
 
 }  // namespace pllm
