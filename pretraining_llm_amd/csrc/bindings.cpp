@@ -809,6 +809,43 @@ Tensor sample(const Tensor& logits, double temperature, int64_t seed) {
   return out;
 }
 
+// per-row samplers: every parameter a [B] device tensor (values cannot be checked here: they live
+// on the device, and the kernel treats out-of-range ones as "filter off" / clamps them)
+// -> tokens int64 [B, 1], kept int32 [B], min_kept fp32 [B]
+std::tuple<Tensor, Tensor, Tensor> sample_rows(const Tensor& logits, const Tensor& temperature, const Tensor& top_k,
+                                               const Tensor& top_p, const Tensor& min_p, const Tensor& seed,
+                                               const Tensor& step) {
+  check_gpu(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "sample_rows: logits [B, V] with unit column stride");
+  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16,
+              "sample_rows: logits must be float32 or bfloat16");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V > 0 && V < (1ll << 31), "sample_rows: vocabulary size");
+  TORCH_CHECK(logits.stride(0) >= 0, "sample_rows: negative row stride");
+  auto check_param = [&](const Tensor& t, at::ScalarType ty, const char* name) {
+    check_gpu(t, name);
+    TORCH_CHECK(t.device() == logits.device(), "sample_rows: ", name, " must be on the logits' device");
+    TORCH_CHECK(t.scalar_type() == ty, "sample_rows: ", name, " must be ", ty, ", got ", t.scalar_type());
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == B && t.is_contiguous(), "sample_rows: ", name,
+                " must be a contiguous [B] tensor");
+  };
+  check_param(temperature, at::kFloat, "temperature");
+  check_param(top_k, at::kInt, "top_k");
+  check_param(top_p, at::kFloat, "top_p");
+  check_param(min_p, at::kFloat, "min_p");
+  check_param(seed, at::kLong, "seed");
+  check_param(step, at::kLong, "step");
+  Tensor tokens = at::empty({B, 1}, logits.options().dtype(at::kLong));
+  Tensor kept = at::empty({B}, logits.options().dtype(at::kInt));
+  Tensor min_kept = at::empty({B}, logits.options().dtype(at::kFloat));
+  if (B > 0)
+    pllm::sample_rows(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, logits.stride(0), (int)B, (int)V,
+                      temperature.data_ptr<float>(), top_k.data_ptr<int>(), top_p.data_ptr<float>(),
+                      min_p.data_ptr<float>(), seed.data_ptr<int64_t>(), step.data_ptr<int64_t>(),
+                      tokens.data_ptr<int64_t>(), kept.data_ptr<int>(), min_kept.data_ptr<float>(), cur_stream());
+  return {tokens, kept, min_kept};
+}
+
 // ---------------------------------------------------------------- attention
 void check_head_view(const Tensor& t, const char* name, int64_t D) {
   check_bf16(t, name);
@@ -1076,6 +1113,7 @@ TORCH_LIBRARY(pllm, m) {
   m.def("transpose_plan(Tensor[] src, Tensor[] dst) -> Tensor");
   m.def("transpose_run(Tensor desc, int total_tiles) -> ()");
   m.def("sample(Tensor logits, float temperature, int seed) -> Tensor");
+  m.def("sample_rows(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor min_p, Tensor seed, Tensor step) -> (Tensor tokens, Tensor kept, Tensor min_kept)");
   m.def("attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale) -> Tensor[]");
   m.def("attn_decode(Tensor q, Tensor k, Tensor v, float scale, Tensor? seqlen=None) -> Tensor");
   m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, Tensor? delta=None) -> ()");
@@ -1108,6 +1146,7 @@ TORCH_LIBRARY_IMPL(pllm, CUDA, m) {
   m.impl("transpose_plan", transpose_plan);
   m.impl("transpose_run", transpose_run);
   m.impl("sample", sample);
+  m.impl("sample_rows", sample_rows);
   m.impl("attn_fwd", attn_fwd);
   m.impl("attn_decode", attn_decode);
   m.impl("gemv", gemv);

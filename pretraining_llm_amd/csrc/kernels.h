@@ -167,6 +167,12 @@ void transpose_batch(const int64_t* desc, int n, int total_tiles, hipStream_t st
 void sample_tokens(const void* logits, bool bf16_in, int64_t ld, int B, int V, float temperature, uint64_t seed,
                    int64_t* out, hipStream_t st);
 
+// sampling_rows.hip: per-row temperature / top-k / top-p / min-p Gumbel-max draw, every parameter a
+// device array of B entries; uniforms keyed by (seed[row], step[row], column) only
+void sample_rows(const void* logits, bool bf16_in, int64_t ld, int B, int V, const float* temperature,
+                 const int* top_k, const float* top_p, const float* min_p, const int64_t* seed, const int64_t* step,
+                 int64_t* tokens, int* kept, float* min_kept, hipStream_t st);
+
 // gemv.hip: y[M, N] = act(in[M, K] W[N, K]^T + bias) for M <= gemv_max_rows() (decode projections),
 // in = x, or norm(x + res) with the residual stream x + res written to s_out when gamma is set
 struct GemvArgs {

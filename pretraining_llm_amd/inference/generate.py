@@ -14,6 +14,7 @@ semantics are reproduced exactly by re-prefilling the cropped window.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -119,13 +120,69 @@ class DecodeGraph:
         return self.logits
 
 
+def filter_logits(logits: torch.Tensor, temperature: float, top_k: Optional[int] = None,
+                  top_p: Optional[float] = None, min_p: Optional[float] = None) -> torch.Tensor:
+    """z = logits / temperature with everything outside the kept set at -inf (torch ops, any device).
+
+    The semantics of csrc/sampling_rows.hip: every filter is a VALUE threshold over the valid entries
+    (not NaN, not -inf), so ties stay together -- top-k keeps z >= the k-th largest value; top-p, on the
+    top-k survivors of mass M with w = exp(z - z_max), keeps z >= t for the largest t with
+    mass{z >= t} >= p * M; min-p keeps z >= z_max + ln(min_p).  The tightest threshold wins."""
+    inv_t = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(temperature), dtype=torch.float32)
+    z = logits.double() * inv_t.double().item()
+    z = torch.where(torch.isnan(z), torch.full_like(z, float("-inf")), z)
+    V = z.shape[-1]
+    zmax = z.max(-1, keepdim=True).values
+    thr = torch.full_like(zmax, float("-inf"))
+    if top_k is not None and 0 < top_k < V:
+        thr = torch.topk(z, top_k).values[:, [-1]]  # -inf (= off) where fewer than k entries are valid
+    if top_p is not None and top_p < 1.0:
+        zs = z.sort(-1, descending=True).values
+        w = torch.where(zs >= thr, torch.exp(zs - zmax), torch.zeros_like(zs))
+        w = torch.where(torch.isnan(w), torch.zeros_like(w), w)  # a row without a valid entry
+        cum = w.cumsum(-1)
+        j = (cum >= max(float(top_p), 0.0) * cum[:, [-1]]).int().argmax(-1, keepdim=True)
+        thr = torch.maximum(thr, zs.gather(-1, j))
+    if min_p is not None and min_p > 0.0:
+        thr = torch.maximum(thr, zmax + math.log(min(float(min_p), 1.0)))
+    return z.masked_fill(z < thr, float("-inf")).float()
+
+
 def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[int] = None,
-                generator: Optional[torch.Generator] = None) -> torch.Tensor:
+                generator: Optional[torch.Generator] = None, top_p: Optional[float] = None,
+                min_p: Optional[float] = None, seed: Optional[int] = None, step: int = 0) -> torch.Tensor:
     """logits [B, V] (fp32) -> next token ids [B, 1]; temperature 0 = greedy.
 
     On the GPU the draw is one fused Gumbel-max kernel (csrc/sampling.hip: an exact sample
     of softmax(logits / T) in a single pass, seeded from ``generator``); on the CPU it is the
-    reference's softmax + multinomial (transformer.py:111-112)."""
+    reference's softmax + multinomial (transformer.py:111-112).
+
+    ``top_p`` / ``min_p`` (nucleus / minimum-probability truncation) or an integer ``seed`` take the
+    per-row kernel on the GPU (csrc/sampling_rows.hip: top-k, top-p and min-p inside the one launch,
+    no host sync).  With ``seed`` the uniforms are a function of (seed + row, step, column) alone --
+    ``step`` is the index of the token being drawn -- so a sequence's tokens do not depend on what
+    shares its batch; without it each call draws fresh row seeds from ``generator``."""
+    rows = top_p is not None or min_p is not None or seed is not None
+    if rows and temperature != 0.0 and logits.is_cuda and ops.get_backend() == "auto":
+        B, dev = logits.shape[0], logits.device
+        if seed is not None:
+            seeds = torch.arange(B, dtype=torch.long, device=dev) + int(seed)
+        else:
+            gdev = generator.device if generator is not None else "cpu"
+            seeds = torch.randint(0, 2 ** 62, (B,), generator=generator, device=gdev).to(dev, non_blocking=True)
+
+        def full(v, dt):
+            return torch.full((B,), v, dtype=dt, device=dev)
+        return ops._ops().sample_rows(logits, full(float(temperature), torch.float32),
+                                      full(int(top_k or 0), torch.int32),
+                                      full(1.0 if top_p is None else float(top_p), torch.float32),
+                                      full(0.0 if min_p is None else float(min_p), torch.float32),
+                                      seeds, full(int(step), torch.long))[0]
+    if rows and temperature != 0.0:
+        if generator is None and seed is not None:
+            generator = torch.Generator(device=logits.device).manual_seed((int(seed) * 1000003 + int(step)) % 2 ** 62)
+        probs = torch.softmax(filter_logits(logits, temperature, top_k, top_p, min_p), dim=-1)
+        return torch.multinomial(probs, num_samples=1, generator=generator)
     if top_k is not None and top_k < logits.shape[-1] and temperature != 0.0:
         v, _ = torch.topk(logits, top_k)
         logits = logits.masked_fill(logits < v[:, [-1]], float("-inf"))
@@ -144,8 +201,10 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[
 @torch.no_grad()
 def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
              use_cache: bool = True, generator: Optional[torch.Generator] = None,
-             cuda_graph: bool = False, decode_cache: Optional[dict] = None) -> torch.Tensor:
-    """``cuda_graph``: replay each single-token step from one captured hipGraph (GPU only).
+             cuda_graph: bool = False, decode_cache: Optional[dict] = None, top_p: Optional[float] = None,
+             min_p: Optional[float] = None, seed: Optional[int] = None) -> torch.Tensor:
+    """``top_p`` / ``min_p`` / ``seed``: see ``sample_next`` (token ``n`` of the call is drawn at step ``n``).
+    ``cuda_graph``: replay each single-token step from one captured hipGraph (GPU only).
     ``decode_cache``: a dict owned by the caller (e.g. the generation service) that keeps the KV
     cache and the captured decode graph per (batch, cache length) across calls, so a repeated
     shape skips the allocation and the capture (the prefill overwrites the rows a call reads)."""
@@ -156,10 +215,10 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float =
     learned = cfg.pos == "learned"
     try:
         if not use_cache:
-            for _ in range(max_new_tokens):
+            for step in range(max_new_tokens):
                 idx_cond = idx[:, -ctx_len:]
                 logits, _ = model(idx_cond)
-                nxt = sample_next(logits[:, -1, :].float(), temperature, top_k, generator)
+                nxt = sample_next(logits[:, -1, :].float(), temperature, top_k, generator, top_p, min_p, seed, step)
                 idx = torch.cat([idx, nxt], dim=1)
             return idx
         B = idx.shape[0]
@@ -180,7 +239,7 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float =
         logits = forward_cached(model, window, cache, 0)
         pos = window.shape[1]
         for step in range(max_new_tokens):
-            nxt = sample_next(logits, temperature, top_k, generator)
+            nxt = sample_next(logits, temperature, top_k, generator, top_p, min_p, seed, step)
             idx = torch.cat([idx, nxt], dim=1)
             if step == max_new_tokens - 1:
                 break

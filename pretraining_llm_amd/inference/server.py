@@ -17,6 +17,7 @@ app (POST /generate, GET /health, GET /stats); ``scripts/serve.py`` runs it unde
 """
 
 import queue
+import struct
 import threading
 import time
 from concurrent.futures import Future
@@ -34,13 +35,16 @@ class GenRequest:
     top_k: Optional[int] = None
     seed: Optional[int] = None
     t_submit: float = field(default_factory=time.perf_counter)
+    top_p: Optional[float] = None   # nucleus sampling: the smallest set of mass >= top_p (None / >= 1: off)
+    min_p: Optional[float] = None   # drop tokens below min_p x the top probability (None / <= 0: off)
 
     def group_key(self):
         # sequences decode in lockstep: one prompt length, one number of steps, one sampler.  A
         # seeded request is never batched with another: its tokens must not depend on its row or
         # on its batch-mates, so it decodes alone with its own generator (= single-request generate)
         private = id(self) if self.seed is not None else None
-        return (len(self.tokens), self.max_new_tokens, float(self.temperature), self.top_k, self.seed, private)
+        return (len(self.tokens), self.max_new_tokens, float(self.temperature), self.top_k, self.seed, private,
+                self.top_p, self.min_p)
 
 
 @dataclass
@@ -142,7 +146,7 @@ class GenerationServer:
             with torch.no_grad():
                 out = self.model.generate(idx, max_new_tokens=req0.max_new_tokens, temperature=req0.temperature,
                                           top_k=req0.top_k, generator=gen, cuda_graph=self.cuda_graph,
-                                          decode_cache=self._decode_cache)
+                                          decode_cache=self._decode_cache, top_p=req0.top_p, min_p=req0.min_p)
             out = out.tolist()
             while len(self._decode_cache) > self.max_cached_shapes:  # oldest shape first
                 self._decode_cache.pop(next(iter(self._decode_cache)))
@@ -162,7 +166,7 @@ class GenerationServer:
 
 
 def create_app(server: GenerationServer, tokenizer=None):
-    """FastAPI app: POST /generate {prompt | tokens, max_new_tokens, temperature, top_k, seed},
+    """FastAPI app: POST /generate {prompt | tokens, max_new_tokens, temperature, top_k, top_p, min_p, seed},
     GET /health, GET /stats."""
     import asyncio
 
@@ -175,6 +179,8 @@ def create_app(server: GenerationServer, tokenizer=None):
         max_new_tokens: int = 64
         temperature: float = 1.0
         top_k: Optional[int] = None
+        top_p: Optional[float] = None
+        min_p: Optional[float] = None
         seed: Optional[int] = None
 
     app = FastAPI(title="pretraining-llm-amd generation")
@@ -200,7 +206,8 @@ def create_app(server: GenerationServer, tokenizer=None):
                 raise HTTPException(400, "no tokenizer loaded: send 'tokens'")
             toks = tokenizer.encode_ordinary(body.prompt) or [tokenizer.eot_token % cfg.vocab_size]
         try:
-            fut = server.submit(GenRequest(toks, body.max_new_tokens, body.temperature, body.top_k, body.seed))
+            fut = server.submit(GenRequest(toks, body.max_new_tokens, body.temperature, body.top_k, body.seed,
+                                           top_p=body.top_p, min_p=body.min_p))
         except ValueError as e:
             raise HTTPException(400, str(e))
         res: GenResult = await asyncio.wrap_future(fut)
@@ -221,6 +228,13 @@ class ContinuousGenerationServer:
     tensors -- csrc/attn_decode.hip, csrc/gemv.hip -- so the step is one hipGraph replay for the
     whole slot set), and a finished sequence leaves without waiting for the others.  Unlike the
     lockstep ``GenerationServer`` no request waits for company of the same prompt length.
+
+    On the GPU every slot's sampler (temperature, top-k, top-p, min-p, seed) sits in device arrays
+    written at admission, and ONE csrc/sampling_rows.hip launch per step draws the whole slot set,
+    whatever the mix of samplers.  A request's uniforms are a function of (its seed, the index of
+    the token being drawn, the vocabulary column) alone, so a seeded request gets the same tokens
+    whatever shares the batch -- the tokens of ``generate(..., seed=seed)`` with the same sampler on
+    the same prompt; an unseeded one draws its seed from the host RNG once, at admission.
 
     Learned absolute positions (arch ref / gpt2) follow the reference's crop semantics: a slot
     whose sequence reaches ``context_length`` is re-prefilled on its last ``context_length``
@@ -247,6 +261,14 @@ class ContinuousGenerationServer:
         # generated tokens, so a decode step needs no host <-> device round trip
         self.tok_d = torch.zeros(self.B, 1, dtype=torch.long, device=self.device)
         self.out_d = torch.zeros(self.B, 256, dtype=torch.long, device=self.device)
+        # per-slot sampler parameters of the fused sampling launch (GPU): a host mirror (six int32 words
+        # per slot), shipped whole (one async copy, no kernel) whenever an admission changes it
+        from .. import ops
+        self.fused = self.device.type == "cuda" and ops.get_backend() == "auto"  # HIP sampling kernel
+        self.samp_h = self.samp_d = None
+        if self.fused:
+            self.samp_h = [(0, 0, 0, 0, 0, 0)] * self.B  # idle slots: greedy
+            self.samp_d = self._ship_samplers(self.samp_h)
         self._q = queue.Queue()
         self._stop = threading.Event()
         self._submit_lock = threading.Lock()
@@ -325,38 +347,82 @@ class ContinuousGenerationServer:
         with torch.no_grad():
             return forward_cached(self.model, idx, self._slot_cache(s), 0), len(window)
 
+    @staticmethod
+    def _sampler_words(req: GenRequest, seed: int) -> tuple:
+        """A request's sampler as the six int32 words the device arrays hold: seed (low, high), temperature,
+        top_k, top_p, min_p (floats as their fp32 bits)."""
+        lo, hi, t, p, mp = struct.unpack("<5i", struct.pack(
+            "<q3f", seed, float(req.temperature), 1.0 if req.top_p is None else float(req.top_p),
+            0.0 if req.min_p is None else float(req.min_p)))
+        return (lo, hi, t, min(max(int(req.top_k or 0), 0), 2 ** 31 - 1), p, mp)
+
+    def _ship_samplers(self, samplers: List[tuple]):
+        """One async copy of n samplers, packed [seed (2 n) | temperature (n) | top_k (n) | top_p (n) | min_p (n)],
+        -> the (temperature, top_k, top_p, min_p, seed) device views ``sample_rows`` takes."""
+        n = len(samplers)
+        words = [0] * (6 * n)
+        for j, (lo, hi, t, k, p, mp) in enumerate(samplers):
+            words[2 * j], words[2 * j + 1] = lo, hi
+            words[2 * n + j], words[3 * n + j], words[4 * n + j], words[5 * n + j] = t, k, p, mp
+        d = self._dev_index(words, torch.int32)
+        return (d[2 * n:3 * n].view(torch.float32), d[3 * n:4 * n], d[4 * n:5 * n].view(torch.float32),
+                d[5 * n:6 * n].view(torch.float32), d[:2 * n].view(torch.long))
+
+    def _sample_record(self, rows: List[int], logits: torch.Tensor, per_slot: bool = False):
+        """Draw the next token of each slot in ``rows`` and append it on the device.  ``logits`` has one
+        row per entry of ``rows``, or (``per_slot``) one row per slot of the server."""
+        from .. import ops
+        idx = self._dev_index(rows)
+        cols = self._dev_index([self.slots[s]["n_new"] for s in rows])  # = the index of the token drawn
+        if not self.fused:  # torch ops (CPU, or the torch backend)
+            if per_slot and len(rows) != self.B:
+                logits = logits.index_select(0, idx)
+            toks = self._sample(rows, logits)
+        else:
+            # ONE launch for any mix of samplers; idle slots of a per-slot batch draw a token nobody reads
+            args = self.samp_d
+            if not per_slot:  # a prefill batch: its slots' parameters, packed afresh
+                args = self._ship_samplers([self.slots[s]["sampler"] for s in rows])
+            step = cols
+            if per_slot and len(rows) != self.B:
+                step = torch.zeros(self.B, dtype=torch.long, device=self.device).index_copy_(0, idx, cols)
+            toks = ops._ops().sample_rows(logits, *args, step)[0].view(-1)
+            if per_slot and len(rows) != self.B:
+                toks = toks.index_select(0, idx)
+        self._record(rows, toks, idx, cols)
+
     def _sample(self, rows: List[int], logits: torch.Tensor) -> torch.Tensor:
         """Next token for each slot in ``rows`` (logits row k belongs to slot rows[k]) as a device
-        int64 [len(rows)] tensor (no host sync); slots with the same sampler and no private seed
-        share one fused sampling launch."""
+        int64 [len(rows)] tensor (no host sync), torch-ops path: slots with the same sampler and no
+        private seed share one sampling call."""
         from .generate import sample_next
         groups: Dict[tuple, List[int]] = {}
         for k, s in enumerate(rows):
             r = self.slots[s]["req"]
-            key = (float(r.temperature), r.top_k, s if r.seed is not None else -1)
+            key = (float(r.temperature), r.top_k, s if r.seed is not None else -1, r.top_p, r.min_p)
             groups.setdefault(key, []).append(k)
         if len(groups) == 1:
-            (temp, top_k, private), = groups.keys()
+            (temp, top_k, private, top_p, min_p), = groups.keys()
             gen = self.slots[rows[0]]["gen"] if private >= 0 else None
-            return sample_next(logits, temp, top_k, gen).view(-1)
+            return sample_next(logits, temp, top_k, gen, top_p=top_p, min_p=min_p).view(-1)
         out = torch.empty(len(rows), dtype=torch.long, device=logits.device)
-        for (temp, top_k, private), ks in groups.items():
+        for (temp, top_k, private, top_p, min_p), ks in groups.items():
             gen = self.slots[rows[ks[0]]]["gen"] if private >= 0 else None
             idx = self._dev_index(ks)
-            out.index_copy_(0, idx, sample_next(logits.index_select(0, idx), temp, top_k, gen).view(-1))
+            out.index_copy_(0, idx, sample_next(logits.index_select(0, idx), temp, top_k, gen,
+                                                top_p=top_p, min_p=min_p).view(-1))
         return out
 
-    def _dev_index(self, values: List[int]) -> torch.Tensor:
+    def _dev_index(self, values: List[int], dtype=torch.long) -> torch.Tensor:
         # small index lists go through pinned memory with an async copy: no host <-> device sync
-        h = torch.tensor(values, dtype=torch.long).pin_memory() if self.device.type == "cuda" else \
-            torch.tensor(values, dtype=torch.long)
+        h = torch.tensor(values, dtype=dtype).pin_memory() if self.device.type == "cuda" else \
+            torch.tensor(values, dtype=dtype)
         return h.to(self.device, non_blocking=True)
 
-    def _record(self, rows: List[int], toks: torch.Tensor):
-        """Append the sampled tokens of ``rows`` on the device: the decode input buffer and each
-        slot's output row (read back to the host once, when the request finishes)."""
-        idx = self._dev_index(rows)
-        cols = self._dev_index([self.slots[s]["n_new"] for s in rows])
+    def _record(self, rows: List[int], toks: torch.Tensor, idx: torch.Tensor, cols: torch.Tensor):
+        """Append the sampled tokens of ``rows`` (device index ``idx``, output columns ``cols``) on the
+        device: the decode input buffer and each slot's output row (read back to the host once, when
+        the request finishes)."""
         self.tok_d.index_copy_(0, idx, toks.view(-1, 1))
         self.out_d.index_put_((idx, cols), toks.view(-1))
         for s in rows:
@@ -395,13 +461,16 @@ class ContinuousGenerationServer:
             req, fut = it
             s = self.slots.index(None)
             try:
-                gen = None
-                if req.seed is not None:
+                gen, sampler = None, None
+                if self.fused:  # the row's seed: the request's, else one host draw for the whole request
+                    seed = int(req.seed) if req.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+                    sampler = self._sampler_words(req, seed)  # (a value out of range fails the request)
+                elif req.seed is not None:
                     gen = torch.Generator(device=self.device).manual_seed(int(req.seed))
                 if req.max_new_tokens > self.out_d.shape[1]:
                     self._grow_out(req.max_new_tokens)
                 window = req.tokens[-self.ctx:] if self.learned else req.tokens
-                self.slots[s] = {"req": req, "fut": fut, "pos": len(window), "n_new": 0, "gen": gen,
+                self.slots[s] = {"req": req, "fut": fut, "pos": len(window), "n_new": 0, "gen": gen, "sampler": sampler,
                                  "peak_batch": 1, "window": window}
                 admitted.append(s)
             except Exception as e:  # a bad request fails alone
@@ -422,7 +491,11 @@ class ContinuousGenerationServer:
             group = admitted[i:j]
             try:
                 logits = self._prefill_batch(group, [self.slots[s]["window"] for s in group])
-                self._record(group, self._sample(group, logits))
+                if self.fused:
+                    for s in group:
+                        self.samp_h[s] = self.slots[s]["sampler"]
+                    self.samp_d = self._ship_samplers(self.samp_h)
+                self._sample_record(group, logits)
             except Exception as e:
                 for s in group:
                     self.slots[s]["fut"].set_exception(e)
@@ -454,7 +527,7 @@ class ContinuousGenerationServer:
             sl = self.slots[s]
             if self.learned and sl["pos"] >= self.ctx:  # crop semantics: re-prefill the last ctx tokens
                 logits, sl["pos"] = self._prefill(s, self._history(s))
-                self._record([s], self._sample([s], logits))
+                self._sample_record([s], logits)
             else:
                 shared.append(s)
         if shared:
@@ -467,8 +540,7 @@ class ContinuousGenerationServer:
                     logits = self.graph(self.tok_d, pos_t)
                 else:
                     logits = forward_decode(self.model, self.tok_d, self.cache, pos_t, (pos_t + 1).to(torch.int32))
-            sel = logits if len(shared) == self.B else logits.index_select(0, self._dev_index(shared))
-            self._record(shared, self._sample(shared, sel))
+            self._sample_record(shared, logits, per_slot=True)
             for s in shared:
                 self.slots[s]["pos"] += 1
             self.stats["decode_steps"] += 1

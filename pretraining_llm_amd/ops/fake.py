@@ -153,6 +153,12 @@ def register() -> None:
     def _(logits, temperature, seed):
         return logits.new_empty((logits.shape[0], 1), dtype=torch.int64)
 
+    @_reg("sample_rows")
+    def _(logits, temperature, top_k, top_p, min_p, seed, step):
+        B = logits.shape[0]
+        return (logits.new_empty((B, 1), dtype=torch.int64), logits.new_empty((B,), dtype=torch.int32),
+                logits.new_empty((B,), dtype=torch.float32))
+
     @_reg("attn_fwd")
     def _(q, k, v, causal, scale):
         B, T, H, _ = q.shape

@@ -7,7 +7,7 @@
 # checkpoint's ``model_config`` when present (else from config.config, like the
 # reference), wrapper prefixes are stripped before the strict load (D7), the
 # device falls back to CPU when no GPU is present, generation uses the KV cache,
-# and --temperature/--top_k/--device/--dtype are optional extras.  --dtype: the
+# and --temperature/--top_k/--top_p/--min_p/--device/--dtype are optional extras.  --dtype: the
 # reference runs the fp32 model on the device (generate_text.py:21-42) -- ``float32``
 # does that here too (torch ops, eager decode); the default ``auto`` is bf16 on the
 # HIP kernels with the hipGraph decode step on a GPU and fp32 on the CPU.
@@ -46,8 +46,10 @@ def load_model(model_path: str, device: str, dtype: str = "auto"):
 
 
 def generate_tokens(model_path: str, start_ids, max_new_tokens: int = 100, device: str = 'cuda', dtype: str = "auto",
-                    temperature: float = 1.0, top_k=None, seed=None, cuda_graph: bool = True):
-    """Token-level generation (prompt ids -> prompt + new ids)."""
+                    temperature: float = 1.0, top_k=None, seed=None, cuda_graph: bool = True, top_p=None, min_p=None):
+    """Token-level generation (prompt ids -> prompt + new ids).  With ``top_p`` / ``min_p`` a ``seed`` keys
+    the per-row sampler directly (the tokens a server request with that seed gets); without them it
+    seeds a torch.Generator as before."""
     if device.startswith("cuda") and not torch.cuda.is_available():
         device = "cpu"
     model = load_model(model_path, device, dtype)
@@ -59,11 +61,13 @@ def generate_tokens(model_path: str, start_ids, max_new_tokens: int = 100, devic
     graph = cuda_graph and device.startswith("cuda") and _dtype(device, dtype) == torch.bfloat16
     with torch.no_grad():
         return model.generate(context, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k,
-                              generator=gen, cuda_graph=graph)[0].tolist()
+                              generator=gen, cuda_graph=graph, top_p=top_p, min_p=min_p,
+                              seed=seed if (top_p is not None or min_p is not None) else None)[0].tolist()
 
 
 def generate_text(model_path: str, input_text: str, max_new_tokens: int = 100, device: str = 'cuda',
-                  temperature: float = 1.0, top_k=None, seed=None, cuda_graph: bool = True, dtype: str = "auto") -> str:
+                  temperature: float = 1.0, top_k=None, seed=None, cuda_graph: bool = True, dtype: str = "auto",
+                  top_p=None, min_p=None) -> str:
     from pretraining_llm_amd.data.tokenizer import get_tokenizer
     from pretraining_llm_amd.utils.checkpoint import load_checkpoint
     enc = get_tokenizer(config.get('tokenizer_name', 'gpt2'))
@@ -71,7 +75,8 @@ def generate_text(model_path: str, input_text: str, max_new_tokens: int = 100, d
     if not start_ids:
         vocab = load_checkpoint(model_path).get("model_config", {}).get("vocab_size", config['vocab_size'])
         start_ids = [enc.eot_token % vocab]
-    tokens = generate_tokens(model_path, start_ids, max_new_tokens, device, dtype, temperature, top_k, seed, cuda_graph)
+    tokens = generate_tokens(model_path, start_ids, max_new_tokens, device, dtype, temperature, top_k, seed, cuda_graph,
+                             top_p, min_p)
     return enc.decode(tokens)
 
 
@@ -83,13 +88,16 @@ def main() -> None:
     parser.add_argument('--device', type=str, default='cuda')
     parser.add_argument('--temperature', type=float, default=1.0)
     parser.add_argument('--top_k', type=int, default=None)
+    parser.add_argument('--top_p', type=float, default=None, help='nucleus sampling: smallest set of mass >= top_p')
+    parser.add_argument('--min_p', type=float, default=None, help='drop tokens below min_p x the top probability')
     parser.add_argument('--seed', type=int, default=None)
     parser.add_argument('--dtype', type=str, default='auto', choices=['auto', 'bfloat16', 'float32'],
                         help="auto: bf16 HIP kernels on a GPU, fp32 on the CPU; float32: the reference's precision")
     parser.add_argument('--no_cuda_graph', action='store_true', help='eager decode steps instead of one hipGraph replay')
     args = parser.parse_args()
     generated = generate_text(args.model_path, args.input_text, args.max_new_tokens, args.device,
-                              args.temperature, args.top_k, args.seed, cuda_graph=not args.no_cuda_graph, dtype=args.dtype)
+                              args.temperature, args.top_k, args.seed, cuda_graph=not args.no_cuda_graph, dtype=args.dtype,
+                              top_p=args.top_p, min_p=args.min_p)
     print(f"Generated text:\n{generated}")
 
 

@@ -2,6 +2,7 @@
 #
 #   python scripts/serve.py --model_path models/transformer_B.pt --port 8000
 #   curl -s localhost:8000/generate -d '{"prompt": "Hello", "max_new_tokens": 32}' -H 'content-type: application/json'
+#   (optional per-request sampler fields: "temperature", "top_k", "top_p", "min_p", "seed")
 #
 # Loads the checkpoint like scripts/generate_text.py (reference-format keys, model_config when
 # present) and serves pretraining_llm_amd.inference.server: concurrent requests with the same
