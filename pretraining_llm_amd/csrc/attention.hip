@@ -18,7 +18,7 @@
 //    statistics (m, l) are per-lane scalars and the P^T accumulator is directly
 //    the B operand of O^T += V^T.P^T (no LDS round trip for P).
 //  * backward: one workgroup = NW waves = 32*NW keys of one (batch, kv-head)
-//    (D<=64: 8 waves/256 keys, D=128: 4 waves/128 keys); each
+//    (D <= 64: 8 waves / 256 keys; D = 128: attn_bwd_ks.hip); each
 //    wave keeps dK^T/dV^T for its 32 keys in registers across all query blocks
 //    (and all query heads of a GQA group), so dK/dV need no cross-workgroup sum.
 //    S and dP are computed with the KEY on the lane and initialised with
@@ -29,8 +29,6 @@
 //    per-key-block fp32 slab; a second kernel sums the slabs in a fixed order
 //    (deterministic; the first version's fp32 atomics were its floor).  The key blocks run
 //    in passes so the slab workspace is bounded independently of T (O(T) memory).
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #include "attn_common.h"
@@ -377,9 +375,8 @@ __global__ __launch_bounds__(256) void attn_bwd_pre_kernel(AttnBwdArgs a) {
   if (row < nrows && c == 0) a.delta[((int64_t)b * a.H + h) * a.T + t] = acc;
 }
 
-// Fused-role backward tiling (D = 32 / 64; D = 128 runs the key-stationary kernel of attn_bwd_ks.hip or
-// the role-split kernel below): 8 waves
-// (two per SIMD), each owning 32 keys (BK = 256 keys per workgroup); BQ = 128 query rows per
+// Fused-role backward tiling (D = 32 / 64; D = 128 runs the key-stationary kernel of attn_bwd_ks.hip):
+// 8 waves (two per SIMD), each owning 32 keys (BK = 256 keys per workgroup); BQ = 128 query rows per
 // iteration as NQB = 4 sub-blocks of 32.  KH (32-key halves per wave) stays a parameter of the
 // code.  Measured and removed (same-box A/B, profiles/r2_attn_bwd_removed_variants_ab.jsonl):
 //   * 4 waves x 64 keys (KH = 2, one wave per SIMD): 13-19 % slower at D = 64;
@@ -939,352 +936,6 @@ __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_
   }
 }
 
-// ---------------------------------------------------------------------------
-// Role-split backward ("RS"): one workgroup = 8 waves = 128 keys of one (batch, kv-head) as 4
-// key groups of 32, each group served by a PAIR of waves on one SIMD (w and w + 4):
-//   wave A (w < 4): S = Q K^T -> P (the keys' K rows in registers), dV^T += dO^T P;
-//   wave B (w >= 4): dP = dO V^T (V rows in registers), dS = P (dP - delta) with P handed over
-//   through LDS in the accumulator's own layout (element-wise, fp32), dK^T += Q^T dS, dS^T image.
-// Each wave keeps ONE operand matrix and ONE gradient accumulator (half the registers of the
-// fused-role kernel: two waves per SIMD at D = 128 instead of one, no AGPR shuffling), the two
-// waves of a SIMD overlap one's exp / pack VALU with the other's MFMAs, and the MFMA work per
-// wave is balanced (S + dV vs dP + dK).  dQ as before: per-key-block bf16 slabs, one task per wave.
-template <int D>
-struct RsCfg {
-  static_assert(D == 128, "role-split backward: D = 128");
-  static constexpr int NW = 8, NT = 512, NG = 4;  // waves, threads, key groups (wave pairs)
-  static constexpr int BK = 32 * NG;               // 128 keys per workgroup
-  static constexpr int BQ = 128;                   // queries per iteration (LDS: 145 KiB)
-  static constexpr int NQB = BQ / 32;              // 32-query sub-blocks
-  static constexpr int CPR = D / 8;
-  static constexpr int PX = 2 * NG * 2 * 64 * 4;   // P hand-off (dwords): [parity][group][half][lane] bf16x8
-  static constexpr int LDS_ELEMS = BK * D + 2 * BQ * D + BK * BQ;  // bf16: K, Q, dO, dS^T images
-};
-
-template <int D, bool ROT_BACK>
-__global__ __launch_bounds__(512, 1) void attn_bwd_rs_kernel(AttnBwdArgs a) {
-  using C = RsCfg<D>;
-  using I = Img<D>;
-  static_assert(C::BQ == 128, "dS^T image");
-  using IS = ImgS;  // dS^T image (16-B stores after a half-wave swap: conflict-free, see ImgS)
-  constexpr int NT = C::NT, BK = C::BK, BQ = C::BQ, NQB = C::NQB, CPR = C::CPR;
-  constexpr int NKS = D / 16, NDB = D / 32;
-  __shared__ __attribute__((aligned(16))) uint16_t smem[C::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) uint32_t px[C::PX];
-  __shared__ __attribute__((aligned(16))) float rowc[2 * BQ];  // -lse/scale, -delta
-  uint16_t* Kl = smem;
-  uint16_t* Ql = smem + BK * D;
-  uint16_t* Ol = Ql + BQ * D;
-  uint16_t* Sl = Ol + BQ * D;
-
-  const int BH = a.B * a.Hkv;
-  const int id = blockIdx.x;
-  const int kb = a.kb0 + id / BH;
-  const int bh = id % BH;
-  const int b = bh / a.Hkv, hk = bh % a.Hkv;
-  const int G = a.H / a.Hkv;
-  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, hh = lane >> 5;
-  const bool roleA = w < C::NG;  // wave-uniform
-  const int grp = w & (C::NG - 1);
-  const int k0 = kb * BK;
-  const int kw0 = k0 + grp * 32;
-  const int off = a.S - a.T;
-  const uint16_t* kp = a.k + b * a.k_sb + (int64_t)hk * a.k_sh;
-  const uint16_t* vp = a.v + b * a.v_sb + (int64_t)hk * a.v_sh;
-
-  // this lane's key row of V (wave B) as B-operand fragments; wave A reads its K fragments back
-  // from the K image below, so K crosses HBM / L2 once per workgroup
-  bf16x8 kvf[NKS];
-  if (!roleA) {
-    const int key = kw0 + r;
-    const uint16_t* src = vp + (int64_t)key * a.v_st;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) kvf[ks] = key < a.S ? as_frag(ld16(src + 16 * ks + 8 * hh)) : zero_frag();
-  }
-  // whole K block into LDS for the S (wave A) and dQ products
-  constexpr int CPR2 = CPR / 2;
-#pragma unroll
-  for (int i = 0; i < (BK * CPR2 + NT - 1) / NT; ++i) {
-    const int c = tid + NT * i, row = c / CPR2, col = c % CPR2, kk = k0 + row;
-    if (c < BK * CPR2) {
-      u32x4 lo = u32x4{0u, 0u, 0u, 0u}, hi = lo;
-      if (kk < a.S) {
-        lo = ld16(kp + (int64_t)kk * a.k_st + col * 8);
-        hi = ld16(kp + (int64_t)kk * a.k_st + (col + CPR2) * 8);
-      }
-      I::st_pair(Kl, row, col, lo, hi);
-    }
-  }
-  vm_wait_all();
-  __syncthreads();
-  if (roleA) {
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) kvf[ks] = as_frag(ld16(Kl + grp * 32 * D + (I::off(r, 8 * hh) ^ (ks << 4))));
-  }
-
-  f32x16 acc[NDB];  // dV^T (wave A) or dK^T (wave B) of the group's 32 keys
-#pragma unroll
-  for (int db = 0; db < NDB; ++db) acc[db] = zero16();
-  const float c2 = a.scale_log2;
-  const int g1 = (lane >> 4) & 1, i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;
-  const int nqb = (a.T + BQ - 1) / BQ;
-  int qb_start = 0;
-  if (a.causal) qb_start = max(0, k0 - off) / BQ;
-  const int per_head = nqb - qb_start;
-  const int total = per_head * G;
-
-  constexpr int QPAIR = (BQ * CPR2 + NT - 1) / NT;
-  u32x4 qr[2 * QPAIR], dor[2 * QPAIR];
-  float rc = 0.f;
-  auto gload = [&](int it) {
-    const int h = hk * G + it / per_head;
-    const int q0 = (qb_start + it % per_head) * BQ;
-    const auto qrs = rows_rsrc(a.q + b * a.q_sb + (int64_t)h * a.q_sh + (int64_t)q0 * a.q_st, a.T - q0, a.q_st, D);
-    const auto ors = rows_rsrc(a.dO + b * a.do_sb + (int64_t)h * a.do_sh + (int64_t)q0 * a.do_st, a.T - q0, a.do_st, D);
-    int tl = tid;
-    asm volatile("" : "+v"(tl));
-#pragma unroll
-    for (int i = 0; i < 2 * QPAIR; ++i) {
-      const int c = tl + NT * (i / 2), row = c / CPR2, col = c % CPR2 + (i & 1) * CPR2;
-      if (c < BQ * CPR2) {
-        qr[i] = buf_ld16(qrs, (uint32_t)(row * (int)a.q_st + col * 8) * 2u);
-        dor[i] = buf_ld16(ors, (uint32_t)(row * (int)a.do_st + col * 8) * 2u);
-      } else {
-        qr[i] = u32x4{0u, 0u, 0u, 0u};
-        dor[i] = u32x4{0u, 0u, 0u, 0u};
-      }
-    }
-    if (tid < 2 * BQ) {
-      const bool isl = __builtin_amdgcn_readfirstlane(tid >> 6) < BQ / 64;
-      const float* base = isl ? a.lse : a.delta;
-      const int q = min(q0 + (tid & (BQ - 1)), a.T - 1);
-      rc = base[((int64_t)b * a.H + h) * a.T + q];
-    }
-  };
-
-  constexpr int NTASK = NQB * NDB;
-  // per-lane LDS element offsets, swizzle applied once (see attn_bwd_kernel): fragment reads
-  // fq ^ (ks << 4) + 32 j D, transposed reads ft0 / ft8 ^ (db << 5) + (32 j + 16 st) D, dS^T
-  // stores fs ^ ((4 j + g) << 3)
-  const int fq = I::off(r, 8 * hh);
-  const int ft0 = I::off(4 * hh + tq, 16 * g1 + 4 * tp), ft8 = I::off(4 * hh + tq + 8, 16 * g1 + 4 * tp);
-  const int fs0 = IS::off(grp * 32 + r, 8 * hh);
-
-  // dQ fragment blocks of an iteration are STORED one iteration late, right after the next
-  // iteration's Q/dO staging: vmcnt counts stores too (gfx9 has no separate store counter), so
-  // stores issued at the end of an iteration would make the next iteration's first wait (for the
-  // prefetched Q/dO) wait out their latency as well (same-box A/B: neutral at the GPT-2 / llama
-  // shapes, where that latency was already covered).
-  constexpr int NTPW = (NTASK + C::NW - 1) / C::NW;
-  u32x4 dqv[NTPW][2];
-  uint16_t* dqp[NTPW];
-#pragma unroll
-  for (int i = 0; i < NTPW; ++i) dqp[i] = nullptr;
-  auto flush_dq = [&]() {
-#pragma unroll
-    for (int i = 0; i < NTPW; ++i)
-      if (dqp[i] != nullptr) {
-        st16(dqp[i], dqv[i][0]);
-        st16(dqp[i] + 8, dqv[i][1]);
-        dqp[i] = nullptr;
-      }
-  };
-  if (total > 0) gload(0);
-  // (head, query block) of iteration it, advanced incrementally (no integer division per step)
-  int h = hk * G, qbi = qb_start;
-  for (int it = 0; it < total; ++it, (++qbi == nqb) ? (qbi = qb_start, ++h) : 0) {
-    const int q0 = qbi * BQ;
-    int fs = fs0;
-    asm volatile("" : "+v"(fs));
-    vm_wait_all();  // prefetch landed on every path (see attn_bwd_kernel)
-    __syncthreads();  // previous iteration's readers of Q / dO / dS^T are done
-#pragma unroll
-    for (int i = 0; i < 2 * QPAIR; i += 2) {
-      const int c = tid + NT * (i / 2), row = c / CPR2, col = c % CPR2;
-      if (c < BQ * CPR2) {
-        I::st_pair(Ql, row, col, qr[i], qr[i + 1]);
-        I::st_pair(Ol, row, col, dor[i], dor[i + 1]);
-      }
-    }
-    if (tid < 2 * BQ) {
-      const bool live = q0 + (tid & (BQ - 1)) < a.T;
-      rowc[tid] = live ? (tid < BQ ? -rc * kLog2e : rc) : 0.f;  // -lse*log2(e), delta
-    }
-    flush_dq();
-    __syncthreads();
-    if (it + 1 < total) gload(it + 1);
-
-    // rows past T need no mask (zero-filled Q / dO rows, row constants 0: see attn_bwd_kernel)
-    const bool need_mask = (k0 + BK > a.S) || (a.causal && k0 + BK - 1 > q0 + off);
-#pragma unroll
-    for (int j = 0; j < NQB; ++j) {
-      const int qj0 = q0 + 32 * j;
-      // causal: the group's keys all after every query of the sub-block -> P = dS = 0
-      const bool live = !a.causal || kw0 <= qj0 + 31 + off;
-      f32x16 x;
-      bf16x8 f0, f1;
-      // the packed bf16 P fragments of this group ([half][lane] 16 B: coalesced b128 accesses);
-      // buffers alternate by sub-block parity (wave B's reads of sub-block j finish before it
-      // reaches barrier j + 1, after which A rewrites the buffer).  B forms dS from this bf16 P,
-      // the same rounding of P that the dV product consumes.
-      uint32_t* pxj = px + ((j & 1) * C::NG + grp) * 2 * 64 * 4;
-      if (live) {
-        // S = Q K^T (wave A) or dP = dO V^T (wave B), key on the lane
-        const uint16_t* Al = roleA ? Ql : Ol;
-        auto chain = [&]() {
-          x = zero16();
-#pragma unroll
-          for (int ks = 0; ks < NKS; ++ks) x = mfma32(as_frag(ld16(Al + 32 * j * D + (fq ^ (ks << 4)))), kvf[ks], x);
-        };
-        if (!roleA) chain();
-        if (roleA) {
-          // P = exp2(S c2 - lse log2e); the mask is a compile-time property of the code path (a
-          // uniform run-time test per element compiles to a branch per exponential) and each
-          // path carries its own MFMA chain (small paths were if-converted into one that always
-          // paid the compare + select)
-          auto expo = [&](auto mask_c) {
-            constexpr bool MASKED = decltype(mask_c)::value;
-            chain();
-            int lo = 0;
-            if constexpr (MASKED) {
-              const int key = kw0 + r;
-              lo = key >= a.S ? 64 : (a.causal ? key - off - (qj0 + 4 * hh) : -64);
-            }
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const f32x4 rs = *reinterpret_cast<const f32x4*>(&rowc[32 * j + 8 * g + 4 * hh]);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                const int i = 4 * g + e;
-                float p = fast_exp2(__builtin_fmaf(x[i], c2, rs[e]));
-                if constexpr (MASKED) p = acc_row(i, 0) < lo ? 0.f : p;
-                x[i] = p;
-              }
-            }
-          };
-          // only the group's diagonal sub-block (or a ragged key end) needs the masked path
-          if (need_mask && ((kw0 + 32 > a.S) || (a.causal && kw0 + 31 > qj0 + off))) expo(std::true_type{});
-          else expo(std::false_type{});
-          f0 = pack_frag(x, 0);
-          f1 = pack_frag(x, 1);
-          *reinterpret_cast<u32x4*>(pxj + lane * 4) = __builtin_bit_cast(u32x4, f0);
-          *reinterpret_cast<u32x4*>(pxj + (64 + lane) * 4) = __builtin_bit_cast(u32x4, f1);
-        }
-      } else if (!roleA) {
-#pragma unroll
-        for (int k = 0; k < 4; k += 2)
-          *reinterpret_cast<u32x4*>(Sl + (fs ^ ((4 * j + k) << 3))) = u32x4{0u, 0u, 0u, 0u};
-      }
-      __syncthreads();  // P of sub-block j handed over
-      if (live) {
-        if (!roleA) {
-          // dS = P (dP - delta) (unscaled); P read back in the same accumulator layout
-          const u32x4 pw[2] = {*reinterpret_cast<const u32x4*>(pxj + lane * 4),
-                               *reinterpret_cast<const u32x4*>(pxj + (64 + lane) * 4)};
-#pragma unroll
-          for (int q4 = 0; q4 < 4; ++q4) {
-            const f32x4 rd = *reinterpret_cast<const f32x4*>(&rowc[BQ + 32 * j + 8 * q4 + 4 * hh]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const int i = 4 * q4 + e;
-              const uint32_t wd = pw[i >> 3][(i & 7) >> 1];
-              x[i] = (x[i] - rd[e]) * ((i & 1) ? hi_bf(wd) : lo_bf(wd));
-            }
-          }
-          f0 = pack_frag(x, 0);
-          f1 = pack_frag(x, 1);
-          // dS^T image from the packed fragments (dwords 2(g&1), 2(g&1)+1 of f[g/2]): group pairs
-          // swapped across the half-waves, one 16-B store of 8 consecutive queries per pair
-          u32x2 v[4];
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const u32x4 w4 = __builtin_bit_cast(u32x4, g < 2 ? f0 : f1);
-            v[g] = u32x2{w4[2 * (g & 1)], w4[2 * (g & 1) + 1]};
-          }
-#pragma unroll
-          for (int k = 0; k < 4; k += 2) {
-#pragma unroll
-            for (int d = 0; d < 2; ++d) {
-              const auto sw = __builtin_amdgcn_permlane32_swap(v[k][d], v[k + 1][d], false, false);
-              v[k][d] = sw[0];
-              v[k + 1][d] = sw[1];
-            }
-            *reinterpret_cast<u32x4*>(Sl + (fs ^ ((4 * j + k) << 3))) = u32x4{v[k][0], v[k][1], v[k + 1][0], v[k + 1][1]};
-          }
-        }
-        // dV^T += dO^T P (A) / dK^T += Q^T dS (B): A operands by transposed reads
-        const uint16_t* Tl = roleA ? Ol : Ql;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) {
-#pragma unroll
-          for (int st = 0; st < 2; ++st) {
-            const int rb = (32 * j + 16 * st) * D;
-            const bf16x8 tA = cat_tr(ds_tr(Tl + rb + (ft0 ^ (db << 5))), ds_tr(Tl + rb + (ft8 ^ (db << 5))));
-            acc[db] = mfma32(tA, st == 0 ? f0 : f1, acc[db]);
-          }
-        }
-      }
-    }
-    __syncthreads();
-    // dQ partial of this key block: one (query sub-block, d-block) task per wave
-#pragma unroll
-    for (int ti = 0; ti < NTPW; ++ti) {
-      const int task = __builtin_amdgcn_readfirstlane(w) + ti * C::NW;
-      if (task >= NTASK) break;
-      const int tq_blk = task / NDB, tdb = task % NDB;
-      const int qt0 = q0 + 32 * tq_blk;
-      if (qt0 >= a.T) continue;  // a query tile past T (ragged last block): no fragment block exists
-      // dQ^T tile = K^T dS^T: the accumulator has the QUERY on the lane and 16 head-dim values
-      // per lane, dumped as one contiguous 2-KiB fragment-order block (two 16-B stores per lane,
-      // coalesced) that attn_dq_reduce_frag_kernel reads back by (query, head-dim) position.
-      // Every key step runs (causal steps past the task's queries read zero dS^T rows: see the
-      // fused-role kernel), so the LDS reads pipeline ahead of the MFMAs
-      f32x16 dqa = zero16();
-      const int qc = 32 * tq_blk + 16 * g1 + 4 * tp, dc = tdb * 32 + 16 * g1 + 4 * tp;
-      const int sa0 = IS::off(8 * hh + tq, qc), sa4 = IS::off(8 * hh + tq + 4, qc);
-      const int ka0 = I::off(8 * hh + tq, dc), ka4 = I::off(8 * hh + tq + 4, dc);
-#pragma unroll
-      for (int ks = 0; ks < BK / 16; ++ks) {
-        const bf16x8 A = cat_tr(ds_tr(Sl + 16 * ks * BQ + sa0), ds_tr(Sl + 16 * ks * BQ + sa4));
-        const bf16x8 Bf = cat_tr(ds_tr(Kl + 16 * ks * D + ka0), ds_tr(Kl + 16 * ks * D + ka4));
-        dqa = mfma32(Bf, A, dqa);
-      }
-      float lo[8], hi[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        lo[e] = dqa[e];
-        hi[e] = dqa[8 + e];
-      }
-      dqv[ti][0] = pack8(lo);
-      dqv[ti][1] = pack8(hi);
-      dqp[ti] = a.dq_acc + (kb - a.kb0) * a.slab +
-                ((((int64_t)b * a.H + h) * a.nqt + (qt0 >> 5)) * NDB + tdb) * 1024 + lane * 16;
-    }
-  }
-  flush_dq();
-  // dV (wave A) / dK scaled and rotated back (wave B) for this lane's key
-  const int key = kw0 + r;
-  if (key >= a.S) return;
-  if (!roleA && ROT_BACK) {
-    const float* cr = a.rope_cos + (int64_t)key * (D / 2);
-    const float* sr = a.rope_sin + (int64_t)key * (D / 2);
-#pragma unroll
-    for (int db = 0; db < NDB / 2; ++db)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int d = db * 32 + 8 * (i >> 2) + 4 * hh + (i & 3);
-        const float c = cr[d], sn = sr[d];
-        const float x0 = acc[db][i], y0 = acc[db + NDB / 2][i];
-        acc[db][i] = x0 * c + y0 * sn;
-        acc[db + NDB / 2][i] = y0 * c - x0 * sn;
-      }
-  }
-  const float sc = roleA ? 1.f : a.scale;
-  uint16_t* dst = roleA ? a.dv + b * a.dv_sb + (int64_t)key * a.dv_st + (int64_t)hk * a.dv_sh
-                        : a.dk + b * a.dk_sb + (int64_t)key * a.dk_st + (int64_t)hk * a.dk_sh;
-  store_row_bf16<NDB>(dst, acc, sc, hh);
-}
-
 // Reduce of the backward kernels' fragment-order dQ slabs.  One workgroup (64 x D/32 threads) per
 // 32-query tile of one (batch, head): thread (d-block blk, lane l) reads its 32 contiguous bytes of
 // the tile's block blk from every slab of the pass (coalesced 2-KiB wave reads; lane l holds query
@@ -1292,8 +943,9 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_rs_kernel(AttnBwdArgs a) {
 // (deterministic) into the fp32 running sum (kept in the same fragment order) or, on the last
 // pass, transposes the tile through LDS and writes dq = scale * total as whole 16-B row chunks,
 // rotated back (ROT_BACK: RoPE, each thread holds a dim chunk and its d + D/2 partner).
-template <int D, int BK, bool ROT_BACK>
+template <int D, bool ROT_BACK>
 __global__ __launch_bounds__(256) void attn_dq_reduce_frag_kernel(AttnBwdArgs a) {
+  constexpr int BK = pllm::kAttnBwdKeyBlock;
   constexpr int NDB = D / 32, NTH = 64 * NDB, LD = D + 4;  // LD: padded fp32 row of the LDS tile
   __shared__ float tile[32 * LD];
   const int tid = threadIdx.x, blk = tid >> 6, lane = tid & 63, hh = lane >> 5;
@@ -1392,24 +1044,6 @@ namespace pllm {
 
 bool attn_supported_head_dim(int D) { return D == 32 || D == 64 || D == 128; }
 
-// key-stationary backward (attn_bwd_ks.hip) per head dim, a bit mask (1: D = 64, 2: D = 128): initial
-// value from PLLM_ATTN_BWD_KS (comma list of head dims, default "128"), runtime A/B via attn_bwd_set_ks
-static int g_attn_ks = -1;
-static bool attn_bwd_ks(int D) {
-  if (g_attn_ks < 0) {
-    const char* e = std::getenv("PLLM_ATTN_BWD_KS");
-    const char* v = e ? e : "128";
-    g_attn_ks = (std::strstr(v, "64") ? 1 : 0) | (std::strstr(v, "128") ? 2 : 0);
-  }
-  return (D == 64 && (g_attn_ks & 1)) || (D == 128 && (g_attn_ks & 2));
-}
-void attn_bwd_set_ks(int mask) { g_attn_ks = mask & 3; }
-
-int attn_bwd_key_block(int D) {
-  if (attn_bwd_ks(D)) return attn_bwd_ks_key_block();
-  return D == 128 ? RsCfg<128>::BK : BwdCfg<64>::BK;
-}
-
 template <int D>
 static void attn_fwd_t(const AttnFwdArgs& a, hipStream_t st) {
   const int nqb = (a.T + FwdCfg<D>::BM - 1) / FwdCfg<D>::BM;
@@ -1424,18 +1058,18 @@ void attn_fwd(const AttnFwdArgs& a, hipStream_t st) {
 
 using BwdKernel = void (*)(AttnBwdArgs);
 
-// One backward over key blocks of BK keys: the delta = rowsum(dO O) pre-pass (skipped when the caller
-// already holds delta), then the key blocks in passes of at most a.nkb_pass (bounded slab workspace);
-// per pass launch_main(a, st) runs the family's main kernel on key blocks [a.kb0, a.kb0 + a.nkb_pass)
+// One backward over key blocks of kAttnBwdKeyBlock keys: the delta = rowsum(dO O) pre-pass (skipped when
+// the caller already holds delta), then the key blocks in passes of at most a.nkb_pass (bounded slab
+// workspace); per pass launch_main(a, st) runs the main kernel on key blocks [a.kb0, a.kb0 + a.nkb_pass)
 // and the ordered reduce sums their dQ slabs (rotating dq back when RoPE tables are given).
-template <int D, int BK, typename LaunchMain>
+template <int D, typename LaunchMain>
 static void attn_bwd_passes(AttnBwdArgs a, hipStream_t st, LaunchMain launch_main) {
+  constexpr int BK = kAttnBwdKeyBlock;
   const int64_t nrows = (int64_t)a.B * a.T * a.H;
   const int pre_grid = (int)((nrows * (D / 8) + 255) / 256);
   const int nkb = (a.S + BK - 1) / BK;
   const int red_grid = a.B * a.H * a.nqt;  // one workgroup per 32-query tile
-  const BwdKernel reduce =
-      a.rope_cos ? attn_dq_reduce_frag_kernel<D, BK, true> : attn_dq_reduce_frag_kernel<D, BK, false>;
+  const BwdKernel reduce = a.rope_cos ? attn_dq_reduce_frag_kernel<D, true> : attn_dq_reduce_frag_kernel<D, false>;
   if (!a.delta_ready) hipLaunchKernelGGL(attn_bwd_pre_kernel<D>, dim3(pre_grid), dim3(256), 0, st, a);
   const int per = a.nkb_pass;
   for (int kb0 = 0; kb0 < nkb; kb0 += per) {
@@ -1446,32 +1080,21 @@ static void attn_bwd_passes(AttnBwdArgs a, hipStream_t st, LaunchMain launch_mai
   }
 }
 
-// launch_main of a main-kernel family of this file: one workgroup of nthreads per (key block of the
-// pass, batch, kv-head); the rotate-back instantiation when RoPE tables are given
-static auto bwd_main(BwdKernel plain, BwdKernel rot_back, int nthreads) {
-  return [=](const AttnBwdArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(a.rope_cos ? rot_back : plain, dim3(a.nkb_pass * a.B * a.Hkv), dim3(nthreads), 0, st, a);
-  };
+// launch_main of the fused-role kernel: one workgroup per (key block of the pass, batch, kv-head); the
+// rotate-back instantiation when RoPE tables are given
+template <int D>
+static void attn_bwd_fused_launch(const AttnBwdArgs& a, hipStream_t st) {
+  static_assert(BwdCfg<D>::BK == kAttnBwdKeyBlock, "one key-block size for every backward kernel");
+  const BwdKernel main = a.rope_cos ? attn_bwd_kernel<D, true> : attn_bwd_kernel<D, false>;
+  hipLaunchKernelGGL(main, dim3(a.nkb_pass * a.B * a.Hkv), dim3(BwdCfg<D>::NT), 0, st, a);
 }
 
-// D = 32 / 64: fused-role kernel; D = 128: role-split kernel; the key-stationary kernel
-// (attn_bwd_ks.hip) where attn_bwd_ks(D).  With RoPE tables q / k arrive rotated and every kernel
-// rotates dq / dk back while storing them.
+// D = 32 / 64: fused-role kernel; D = 128: key-stationary kernel (attn_bwd_ks.hip).  With RoPE tables
+// q / k arrive rotated and every kernel rotates dq / dk back while storing them.
 void attn_bwd(const AttnBwdArgs& a, hipStream_t st) {
-  constexpr int KS_BK = 256;  // attn_bwd_ks_key_block()
-  if (attn_bwd_ks(a.D)) {
-    if (a.D == 64) attn_bwd_passes<64, KS_BK>(a, st, attn_bwd_ks_launch);
-    else attn_bwd_passes<128, KS_BK>(a, st, attn_bwd_ks_launch);
-  } else if (a.D == 32) {
-    attn_bwd_passes<32, BwdCfg<32>::BK>(
-        a, st, bwd_main(attn_bwd_kernel<32, false>, attn_bwd_kernel<32, true>, BwdCfg<32>::NT));
-  } else if (a.D == 64) {
-    attn_bwd_passes<64, BwdCfg<64>::BK>(
-        a, st, bwd_main(attn_bwd_kernel<64, false>, attn_bwd_kernel<64, true>, BwdCfg<64>::NT));
-  } else {
-    attn_bwd_passes<128, RsCfg<128>::BK>(
-        a, st, bwd_main(attn_bwd_rs_kernel<128, false>, attn_bwd_rs_kernel<128, true>, RsCfg<128>::NT));
-  }
+  if (a.D == 32) attn_bwd_passes<32>(a, st, attn_bwd_fused_launch<32>);
+  else if (a.D == 64) attn_bwd_passes<64>(a, st, attn_bwd_fused_launch<64>);
+  else attn_bwd_passes<128>(a, st, attn_bwd_ks_launch);
 }
 
 }  // namespace pllm

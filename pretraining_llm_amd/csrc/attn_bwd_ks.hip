@@ -1,6 +1,6 @@
-// Key-stationary causal flash-attention backward for gfx950 (round 5; D = 64 / 128), replacing the
-// role-split D = 128 kernel of attention.hip.  Reference math: /root/reference/src/models/attention.py:47-57
-// (q k^T * hd^-1/2, causal masked_fill, softmax, @ v), whose backward this is.
+// Key-stationary causal flash-attention backward for gfx950 (round 5), the D = 128 backward (D = 32 / 64
+// run the fused-role kernel of attention.hip).  Reference math: src/models/attention.py:47-57 of the
+// reference (q k^T * hd^-1/2, causal masked_fill, softmax, @ v), whose backward this is.
 //
 // Register-class discipline (the reason this file exists apart from attention.hip): every MFMA is an
 // inline-asm statement with an explicit register class -- the dK^T / dV^T accumulators ("+a") own
@@ -28,16 +28,16 @@
 namespace {
 
 // ---------------------------------------------------------------------------
-// Key-stationary backward ("KS", round 5; D = 64 / 128): one workgroup = 4 waves, ONE per SIMD
+// Key-stationary backward ("KS", round 5; D = 128): one workgroup = 4 waves, ONE per SIMD
 // (512 registers each) = 256 keys of one (batch, kv-head).  Wave w owns keys k0 + 64 w + [0, 64) as
 // two 32-key blocks and keeps, across the whole sweep over the query slices of every query head of
 // the group, their dK^T / dV^T accumulators (D = 128: 256 registers) and their V rows as MFMA B
 // fragments in registers; K lives in one LDS image (S's B fragments by row reads, dQ's A operand by
-// transposed reads).  A slice is BQ = 128 / NDB queries (D = 128: 32, D = 64: 64), so the slice's dQ
+// transposed reads).  A slice is BQ = 128 / NDB = 32 queries, so the slice's dQ
 // tile is exactly 4 tasks of 32 queries x 32 head dims: one per wave, summed over all 256 keys
 // (16 MFMAs) from the slice's dS^T image and stored as one bf16 fragment block per key block (the
-// same slab format as the other kernels, reduced by attn_dq_reduce_frag_kernel<D, 256>).
-// vs the role-split kernel it replaces at D = 128 (128 keys, 8 waves, P handed between wave pairs
+// same slab format as the fused-role kernel, reduced by attn_dq_reduce_frag_kernel<D>).
+// vs the role-split kernel it replaced (removed; 128 keys, 8 waves, P handed between wave pairs
 // through LDS behind a barrier per 32-query sub-block, Q / dO staged through registers): ONE barrier
 // per slice (double-buffered Q / dO / dS^T images and row constants: the next slice's Q / dO DMA is
 // issued right after the barrier and waited just before the next one), half the dQ slab bytes
@@ -46,8 +46,8 @@ namespace {
 // the initial accumulator, one LDS image per operand for row and transposed reads).
 template <int D>
 struct KsCfg {
-  static_assert(D == 64 || D == 128, "key-stationary backward: D = 64 / 128");
-  static constexpr int NW = 4, NT = 256, BK = 256;
+  static_assert(D == 128, "key-stationary backward: D = 128 (D = 64 measured slower than the fused-role kernel)");
+  static constexpr int NW = 4, NT = 256, BK = pllm::kAttnBwdKeyBlock;
   static constexpr int NDB = D / 32, NKS = D / 16;
   static constexpr int NQB = 4 / NDB;        // 32-query sub-blocks per slice (one dQ task per wave)
   static constexpr int BQ = 32 * NQB;        // queries per slice
@@ -59,21 +59,18 @@ struct KsCfg {
   static constexpr int KPPW = BK / QRP / NW; // K image pieces per wave
   static constexpr int TILE = BQ * D;        // elements of one Q (dO) tile
   static constexpr int SIMG = BK * BQ;       // elements of one dS^T image [keys][BQ]
-  static constexpr int LDS_ELEMS = BK * D + 4 * TILE + 2 * SIMG;  // 136 KiB at D = 64 and 128
+  static constexpr int LDS_ELEMS = BK * D + 4 * TILE + 2 * SIMG;  // 136 KiB
 };
 
 // dS^T image [256 keys][W = BQ queries] of the KS kernel: chunk ch (16 B) of row r at ch ^ f(r).
 // Stores: 16 B per lane, 8 consecutive key rows per 8-lane group at one logical chunk -> f is a
 // bijection on 8 consecutive rows modulo the 128-B bank window.  Transposed dQ reads: 4 consecutive
-// rows x the sub-block's 64 B; W = 32: 4 rows = 256 contiguous bytes (any f); W = 64: rows r and r+2
-// share banks, so f(r) ^ f(r + 2) has bit 2 set.  f depends on row bits 0..2 only: +16-row steps are
-// plain additions.
+// rows x the sub-block's 64 B; W = 32: 4 rows = 256 contiguous bytes (any f).  f depends on row bits
+// 0..2 only: +16-row steps are plain additions.
 template <int W>
 struct ImgT {
-  static PL_DEV int f(int r) {
-    if constexpr (W == 32) return (r >> 1) & 3;
-    else return (((r >> 1) & 1) << 2) | ((r & 1) << 1) | ((r >> 2) & 1);
-  }
+  static_assert(W == 32, "dS^T image of a 32-query slice");
+  static PL_DEV int f(int r) { return (r >> 1) & 3; }
   static PL_DEV int off(int r, int col) { return r * W + (((col >> 3) ^ f(r)) << 3) + (col & 7); }
 };
 
@@ -512,24 +509,16 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_ks_kernel(AttnBwdArgs a) {
   }
 }
 
-
 }  // namespace
 
 namespace pllm {
-
-int attn_bwd_ks_key_block() { return KsCfg<128>::BK; }
 
 // one pass of key blocks [a.kb0, a.kb0 + a.nkb_pass) (the caller runs the delta pre-pass before and the
 // slab reduce after)
 void attn_bwd_ks_launch(const AttnBwdArgs& a, hipStream_t st) {
   const dim3 grid(a.nkb_pass * a.B * a.Hkv), blk(256);
-  if (a.D == 64) {
-    if (a.rope_cos) hipLaunchKernelGGL((attn_bwd_ks_kernel<64, true>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((attn_bwd_ks_kernel<64, false>), grid, blk, 0, st, a);
-  } else {
-    if (a.rope_cos) hipLaunchKernelGGL((attn_bwd_ks_kernel<128, true>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((attn_bwd_ks_kernel<128, false>), grid, blk, 0, st, a);
-  }
+  if (a.rope_cos) hipLaunchKernelGGL((attn_bwd_ks_kernel<128, true>), grid, blk, 0, st, a);
+  else hipLaunchKernelGGL((attn_bwd_ks_kernel<128, false>), grid, blk, 0, st, a);
 }
 
 }  // namespace pllm

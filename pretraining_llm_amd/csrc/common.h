@@ -134,6 +134,7 @@ PL_DEV float gelu_df(float x) {
   const float q = x * __builtin_fmaf(6.f * kGeluK * kGeluC, x2, 2.f * kGeluK);
   return __builtin_fmaf(q * s, 1.f - s, s);
 }
+PL_DEV float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }  // SwiGLU
 PL_DEV float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -191,6 +192,41 @@ PL_DEV __amdgpu_buffer_rsrc_t rows_rsrc(const uint16_t* base, int rows, int64_t 
 }
 PL_DEV u32x4 buf_ld16(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
   return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0u, 0));
+}
+// Unconditional buffer ops: a lane with nothing to store / load passes kOff, a byte offset past every
+// descriptor built in this directory (< 2 GiB), and the range check drops the store / returns zeros,
+// so every lane issues every instruction (exact vmcnt counts)
+constexpr uint32_t kOff = 0x80000000u;
+PL_DEV void bst16(__amdgpu_buffer_rsrc_t r, uint32_t off, const u32x4& v) {
+  __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 0);
+}
+
+// ---- MFMA fragments (GEMM, weight-gradient and attention kernels) ----------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+PL_DEV f32x16 mfma32(const bf16x8& a, const bf16x8& b, const f32x16& c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+PL_DEV f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+// element i of a 32x32 accumulator lives at row (i&3) + 8*(i>>2) + 4*half, column lane&31
+PL_DEV int acc_row(int i, int half) { return (i & 3) + 8 * (i >> 2) + 4 * half; }
+// 16 B of an LDS row as a fragment (ds_read_b128)
+PL_DEV bf16x8 lds_frag(const uint16_t* p) { return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(p)); }
+// transposed LDS read (ds_read_b64_tr_b16); two of them (rows r and r + 4) make one fragment
+PL_DEV s16x4 ds_tr(const uint16_t* p) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p); }
+PL_DEV bf16x8 cat_tr(const s16x4& lo, const s16x4& hi) {
+  s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+// grouped order of the 256x256 GEMM output tiles: group_m m-tiles x all n-tiles, m fastest inside a group
+PL_DEV void tile_of(int t, int tiles_m, int tiles_n, int gm, int& tm, int& tn) {
+  const int per_group = gm * tiles_n;
+  const int grp = t / per_group, first_m = grp * gm, gsize = min(gm, tiles_m - first_m);
+  tm = first_m + (t % per_group) % gsize;
+  tn = (t % per_group) / gsize;
 }
 
 // global -> LDS DMA of 16 B per lane into [m0 + 16 * lane] (m0 = wave-uniform LDS byte address)

@@ -8,15 +8,13 @@
 // Every kernel moves 16 B (8 x bf16) per lane per access over a FULL grid (one 16-B vector per
 // thread; the loops still grid-stride for safety): a grid capped at 2048 blocks with
 // grid-stride loops streamed 5.1 TB/s where the full grid streams 6.0-6.2 TB/s on MI355X
-// (GELU fwd / bwd at 402 MB, bench/hbm_probe.py, profiles/r2_elementwise_grid_ab.txt).
+// (GELU fwd / bwd at 402 MB, profiles/r2_elementwise_grid_ab.txt).
 #include <algorithm>
 
 #include "common.h"
 #include "kernels.h"
 
 namespace {
-
-PL_DEV float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 
 inline int ew_grid(size_t n_vec) {
   size_t g = (n_vec + 255) / 256;

@@ -8,7 +8,7 @@
 // with the activation backward and the up-projection's bias-gradient column sums, which
 // otherwise are two full memory-bound passes over the [tokens, 4C] hidden activations
 // (act_fwd_kernel, act_bwd_colsum_kernel).  Reference math: the MLP of
-// /root/reference/src/models/mlp.py:24-26,39-41 (ReLU) and the GPT-2 preset's GELU.
+// the reference's src/models/mlp.py:24-26,39-41 (ReLU) and the GPT-2 preset's GELU.
 //
 // Design (CDNA4), after csrc/gemm_wgrad.hip:
 //  * 256x256 output tile per 512-thread workgroup (8 waves, 2 per SIMD), wave (wm, wn) owns a
@@ -40,8 +40,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int GT = 256;             // output tile (M and N)
 constexpr int GBK = 64;             // K per stage
 constexpr int GNT = 512;            // 8 waves
@@ -50,23 +48,9 @@ constexpr int GSTAGE = 2 * GIMG;    // A image then B image: 64 KiB
 
 PL_DEV int gswz(int row) { return (row >> 1) & 7; }
 PL_DEV int gimg_off(int row, int chunk) { return row * GBK + ((chunk ^ gswz(row)) << 3); }
-PL_DEV bf16x8 lds_frag(const uint16_t* p) { return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(p)); }
 PL_DEV int acc_row32(int e, int half) { return (e & 3) + 8 * (e >> 2) + 4 * half; }
 
-// grouped tile order: GROUP_M m-tiles x all n-tiles, m fastest inside a group
-PL_DEV void tile_of(int t, int tiles_m, int tiles_n, int gm, int& tm, int& tn) {
-  const int per_group = gm * tiles_n;
-  const int grp = t / per_group, first_m = grp * gm, gsize = min(gm, tiles_m - first_m);
-  tm = first_m + (t % per_group) % gsize;
-  tn = (t % per_group) / gsize;
-}
-
-// buffer store / load of 16 B at a per-lane byte offset; an offset past the descriptor's range
-// drops the store / reads zeros, so every lane issues every instruction (exact vmcnt counts)
-constexpr uint32_t kOff = 0x80000000u;  // an offset past every descriptor built here (< 2 GiB)
-PL_DEV void bst16(__amdgpu_buffer_rsrc_t r, uint32_t off, const u32x4& v) {
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 0);
-}
+// 8-B buffer load at a per-lane byte offset (kOff / bst16: common.h)
 PL_DEV u32x2 bld8(__amdgpu_buffer_rsrc_t r, uint32_t off) {
   return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
 }
@@ -81,8 +65,6 @@ constexpr int kEpiOps = EPI == 5 ? 63
                         : EPI == 6 ? 48
                         : EPI == 1 ? 32 + (MF == 32 ? 8 : 4)
                                    : (EPI >= 3 ? 16 + 16 + 2 : 16 + (MF == 32 ? 8 : 4));
-
-PL_DEV float swiglu_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 
 // (acc columns fragments [I0, I0 + NIE) are the wave's 64 columns)
 template <int MF, int EPI, int I0 = 0, typename Acc, int NIA, int NJ>
@@ -218,7 +200,7 @@ PL_DEV void gemm_epilogue(const Acc (&acc)[NIA][NJ], uint16_t* tile, const pllm:
         unpack8(apre2[kk], up);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const float sg = swiglu_sigmoid(gt[e]);
+          const float sg = sigmoid_f(gt[e]);
           du[e] = d[e] * (gt[e] * sg);
           dg[e] = d[e] * up[e] * sg * (1.f + gt[e] * (1.f - sg));
         }
@@ -391,9 +373,10 @@ static int g_gemm_group_m = PL_GEMM_GROUP_M;
 // MFMA groups (hipBLASLt's geometry; 4-18 % slower, its fused epilogues up to 40 % slower)
 // 4 (default): the ping-pong kernel of gemm_pp.hip (two wave groups one barrier apart, counted
 // waits): 4-6 % faster than this file's kernel on every fused epilogue measured (GELU' / SwiGLU' /
-// attention delta; gpurun_out/r4pp7_bench.jsonl, r4ab1_swiglu.jsonl), whole GPT-2 step +0.5 %.
-// This file's kernel remains the FALLBACK for what the ping-pong loop does not take (a single K-tile,
-// K < 128; the delta epilogue with T % 16 != 0); 0 / 2 select it for every shape (tests only)
+// attention delta; profiles/r4_gemm_pp.md), whole GPT-2 step +0.5 %.
+// This file's kernel is the FALLBACK for what the ping-pong loop does not take (a single K-tile,
+// K < 128; the delta epilogue with T % 16 != 0); 0 / 2 select it for every shape (tests only).  Its
+// 32x32x16 and asymmetric-DMA instantiations run only under gemm_set_config from the tests.
 static int g_gemm_phased = 4;
 // CUs the persistent grids leave free, for RCCL kernels overlapping the backward (world > 1)
 static int g_gemm_reserve = 0;

@@ -1,10 +1,11 @@
 // Ping-pong TN GEMM with fused epilogues on gfx950 MFMA (round 4):
 //     C[M, N] = epi( A[M, K] . B[N, K]^T )          (bf16 in, fp32 accumulate, bf16 out)
-// Same contract and epilogues as gemm_tn_kernel (csrc/gemm.hip, which stays as the A/B
-// reference); a structurally different main loop, built for the measured bottleneck of that
-// kernel: its waves parked 36 % of the time on the one barrier + vmcnt(0) per 64-deep K-tile
+// Same contract and epilogues as gemm_tn_kernel (csrc/gemm.hip, the fallback for the calls this
+// kernel does not take -- a single K-tile, or epilogue 6 with T % 16 != 0: gemm_uses_pp -- and the
+// tests' A/B reference); a structurally different main loop, built for the measured bottleneck of
+// that kernel: its waves parked 36 % of the time on the one barrier + vmcnt(0) per 64-deep K-tile
 // (profiles/r3_gemm_tn.md: MFMA busy 41 % vs hipBLASLt's 52 %).  Reference math: the MLP and
-// attention projections of /root/reference/src/models/mlp.py:24-26 and attention.py:29-31.
+// attention projections of the reference's src/models/mlp.py:24-26 and attention.py:29-31.
 //
 // Design (cdna_hip_programming.md §5 "8-phase", T3/T4/T5; MI355X_MICROARCH.md "Two waves per
 // SIMD"):
@@ -49,19 +50,12 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int PT = 256;            // output tile (M and N)
 constexpr int PBK = 64;            // K per K-tile
 constexpr int PNT = 512;           // 8 waves
 constexpr int PIMG = PT * PBK;     // elements of one operand image [256][64]
 constexpr int PSLOT = 2 * PIMG;    // A image then B image: 64 KiB
-constexpr uint32_t kPOff = 0x80000000u;  // a byte offset past every descriptor built here
 
-PL_DEV bf16x8 ldsf(const uint16_t* p) { return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(p)); }
-PL_DEV f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 PL_DEV void pp_barrier() {
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("s_barrier" ::: "memory");
@@ -70,14 +64,6 @@ PL_DEV void pp_barrier() {
 template <int N>
 PL_DEV void pp_vmwait() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// grouped tile order: GROUP_M m-tiles x all n-tiles, m fastest inside a group
-PL_DEV void pp_tile(int t, int tiles_m, int tiles_n, int gm, int& tm, int& tn) {
-  const int per_group = gm * tiles_n;
-  const int grp = t / per_group, first_m = grp * gm, gsize = min(gm, tiles_m - first_m);
-  tm = first_m + (t % per_group) % gsize;
-  tn = (t % per_group) / gsize;
 }
 
 // Two epilogue placements (template flag QE, chosen per call by gemm_pp_quad_epilogue):
@@ -109,11 +95,7 @@ constexpr int kStQ(int q) {
   return EPI == 1 ? 8 : (EPI == 3 || EPI == 4) ? 6 : EPI == 6 ? ((q & 1) ? 8 : 4) : 4;
 }
 
-PL_DEV void pp_st16(__amdgpu_buffer_rsrc_t r, uint32_t off, const u32x4& v) {
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 0);
-}
 PL_DEV float bfr(float x) { return bf2f(f2bf_bits(x)); }  // round to bf16 and back
-PL_DEV float pp_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 
 // ---------------------------------------------------------------------------------------------
 // Epilogue of one 256x256 tile, straight from the accumulators.  Lane (r16 = lane & 15,
@@ -138,7 +120,7 @@ PL_DEV void pp_epilogue(f32x4 (&acc)[4][8], const pllm::GemmArgs& g, int tm, int
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       const bool ok = p == 0 ? cok0 : cok1;
-      unpack8(buf_ld16(brs, ok ? (uint32_t)(colw + 32 * p) * 2u : kPOff), bias[p]);
+      unpack8(buf_ld16(brs, ok ? (uint32_t)(colw + 32 * p) * 2u : kOff), bias[p]);
     }
   }
   float csum[2][8];
@@ -164,9 +146,9 @@ PL_DEV void pp_epilogue(f32x4 (&acc)[4][8], const pllm::GemmArgs& g, int tm, int
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
         const bool ok = p == 0 ? cok0 : cok1;
-        const uint32_t aoff = ok ? (uint32_t)(((int64_t)rt * g.ldaux + colw + 32 * p) * 2) : kPOff;
+        const uint32_t aoff = ok ? (uint32_t)(((int64_t)rt * g.ldaux + colw + 32 * p) * 2) : kOff;
         dst[p] = buf_ld16(ars, aoff);
-        if constexpr (EPI == 5) dst[2 + p] = buf_ld16(ars, ok ? aoff + (uint32_t)N * 2u : kPOff);
+        if constexpr (EPI == 5) dst[2 + p] = buf_ld16(ars, ok ? aoff + (uint32_t)N * 2u : kOff);
       }
     }
   };
@@ -201,8 +183,8 @@ PL_DEV void pp_epilogue(f32x4 (&acc)[4][8], const pllm::GemmArgs& g, int tm, int
     for (int p = 0; p < 2; ++p) {
       const bool ok = p == 0 ? cok0 : cok1;
       const int col = colw + 32 * p;
-      const uint32_t off = ok ? (uint32_t)(((int64_t)rt * g.ldc + col) * 2) : kPOff;
-      const uint32_t aoff = ok ? (uint32_t)(((int64_t)rt * g.ldaux + col) * 2) : kPOff;
+      const uint32_t off = ok ? (uint32_t)(((int64_t)rt * g.ldc + col) * 2) : kOff;
+      const uint32_t aoff = ok ? (uint32_t)(((int64_t)rt * g.ldaux + col) * 2) : kOff;
       float v[8];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -212,7 +194,7 @@ PL_DEV void pp_epilogue(f32x4 (&acc)[4][8], const pllm::GemmArgs& g, int tm, int
       if constexpr (EPI == 0) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += bias[p][e];
-        pp_st16(crs, off, pack8(v));
+        bst16(crs, off, pack8(v));
       } else if constexpr (EPI == 1) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += bias[p][e];
@@ -221,12 +203,12 @@ PL_DEV void pp_epilogue(f32x4 (&acc)[4][8], const pllm::GemmArgs& g, int tm, int
         unpack8(pre, f);  // the activation reads the bf16-rounded pre-activation
 #pragma unroll
         for (int e = 0; e < 8; ++e) f[e] = gelu_f(f[e]);
-        pp_st16(ars, aoff, pre);
-        pp_st16(crs, off, pack8(f));
+        bst16(ars, aoff, pre);
+        bst16(crs, off, pack8(f));
       } else if constexpr (EPI == 2) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e] + bias[p][e], 0.f);
-        pp_st16(crs, off, pack8(v));
+        bst16(crs, off, pack8(v));
       } else if constexpr (EPI == 3 || EPI == 4) {
         float a[8];
         unpack8(axc[p], a);
@@ -236,7 +218,7 @@ PL_DEV void pp_epilogue(f32x4 (&acc)[4][8], const pllm::GemmArgs& g, int tm, int
           v[e] = EPI == 3 ? d * gelu_df(a[e]) : (a[e] > 0.f ? d : 0.f);
         }
         const u32x4 o = pack8(v);
-        pp_st16(crs, off, o);
+        bst16(crs, off, o);
         unpack8(o, v);  // the bias gradient sums the bf16-rounded values, like act_bwd_colsum
 #pragma unroll
         for (int e = 0; e < 8; ++e) csum[p][e] += v[e];
@@ -248,15 +230,15 @@ PL_DEV void pp_epilogue(f32x4 (&acc)[4][8], const pllm::GemmArgs& g, int tm, int
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float d = bfr(v[e]);
-          const float sg = pp_sigmoid(gt[e]);
+          const float sg = sigmoid_f(gt[e]);
           du[e] = d * (gt[e] * sg);
           dg[e] = d * up[e] * sg * (1.f + gt[e] * (1.f - sg));
         }
-        pp_st16(crs, off, pack8(dg));
-        pp_st16(crs, ok ? off + (uint32_t)N * 2u : kPOff, pack8(du));
+        bst16(crs, off, pack8(dg));
+        bst16(crs, ok ? off + (uint32_t)N * 2u : kOff, pack8(du));
       } else {  // EPI 6: dO stored; delta = sum over the wave's 64 columns (one head) of dO * O
         const u32x4 o = pack8(v);
-        pp_st16(crs, off, o);
+        bst16(crs, off, o);
         float d[8], oo[8];
         unpack8(o, d);
         unpack8(axc[p], oo);
@@ -271,7 +253,7 @@ PL_DEV void pp_epilogue(f32x4 (&acc)[4][8], const pllm::GemmArgs& g, int tm, int
       const int m = m0 + rt;
       const int bq = m / g.T, tq = m - bq * g.T, hd = (n0 + wc * 64) >> 6;
       const uint32_t doff = (g4 == 0 && m < M && cok0)
-                                ? (uint32_t)((((int64_t)bq * (N >> 6) + hd) * g.T + tq) * 4) : kPOff;
+                                ? (uint32_t)((((int64_t)bq * (N >> 6) + hd) * g.T + tq) * 4) : kOff;
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, dsum), drs, doff, 0, 0);
     }
     if constexpr (NAX > 0 && !PRE) {
@@ -300,9 +282,9 @@ PL_DEV void pp_epilogue(f32x4 (&acc)[4][8], const pllm::GemmArgs& g, int tm, int
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       const bool ok = (p == 0 ? cok0 : cok1) && r16 == 0;
-      const uint32_t po = ok ? (uint32_t)(colw + 32 * p) * 4u : kPOff;
-      pp_st16(prs, po, __builtin_bit_cast(u32x4, f32x4{csum[p][0], csum[p][1], csum[p][2], csum[p][3]}));
-      pp_st16(prs, ok ? po + 16u : kPOff,
+      const uint32_t po = ok ? (uint32_t)(colw + 32 * p) * 4u : kOff;
+      bst16(prs, po, __builtin_bit_cast(u32x4, f32x4{csum[p][0], csum[p][1], csum[p][2], csum[p][3]}));
+      bst16(prs, ok ? po + 16u : kOff,
               __builtin_bit_cast(u32x4, f32x4{csum[p][4], csum[p][5], csum[p][6], csum[p][7]}));
     }
   }
@@ -319,8 +301,8 @@ PL_DEV void pp_epilogue_swiglu(f32x4 (&acc)[4][8], const pllm::GemmArgs& g, int 
   const int r16 = lane & 15, g4 = lane >> 4;
   const int col = n0 + wc * 32 + 8 * g4;
   const bool ok = col < F;
-  const uint32_t off = ok ? (uint32_t)(((int64_t)r16 * g.ldc + col) * 2) : kPOff;
-  const uint32_t aoff = ok ? (uint32_t)(((int64_t)r16 * g.ldaux + col) * 2) : kPOff;
+  const uint32_t off = ok ? (uint32_t)(((int64_t)r16 * g.ldc + col) * 2) : kOff;
+  const uint32_t aoff = ok ? (uint32_t)(((int64_t)r16 * g.ldaux + col) * 2) : kOff;
   const int rows_ok = min(PT, M - m0);
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -340,10 +322,10 @@ PL_DEV void pp_epilogue_swiglu(f32x4 (&acc)[4][8], const pllm::GemmArgs& g, int 
     unpack8(gp, gt);
     unpack8(upk, up);
 #pragma unroll
-    for (int q = 0; q < 8; ++q) gt[q] = gt[q] * pp_sigmoid(gt[q]) * up[q];
-    pp_st16(ars, aoff, gp);
-    pp_st16(ars, ok ? aoff + (uint32_t)F * 2u : kPOff, upk);
-    pp_st16(crs, off, pack8(gt));
+    for (int q = 0; q < 8; ++q) gt[q] = gt[q] * sigmoid_f(gt[q]) * up[q];
+    bst16(ars, aoff, gp);
+    bst16(ars, ok ? aoff + (uint32_t)F * 2u : kOff, upk);
+    bst16(crs, off, pack8(gt));
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -457,7 +439,7 @@ PL_DEV void pp_aux_issue(const PPCtx& c, const PPEpi& e) {
   if constexpr (EPI <= 2) {
     const bool has = e.valid && g.bias != nullptr && col0 < g.N;
     const i32x4v srd = srd_of(g.bias != nullptr ? g.bias + (has ? col0 : 0) : g.A, has ? (uint32_t)(g.N - col0) * 2u : 0u);
-    blds16(srd, c.lane < 4 ? (uint32_t)c.lane * 16u : kPOff, dst);  // lanes 0-3: 8 columns each
+    blds16(srd, c.lane < 4 ? (uint32_t)c.lane * 16u : kOff, dst);  // lanes 0-3: 8 columns each
   } else {
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
@@ -488,8 +470,8 @@ PL_DEV void pp_epi_quad(f32x4 (&acc)[4][8], const PPCtx& c, const PPEpi& e, cons
   const bool ok = col < N;
   // per row tile j a descriptor based at its first row (scalar), so the per-lane offsets are
   // the same for every j: one VGPR each instead of eight hoisted row offsets (those spilled)
-  const uint32_t off = ok ? (uint32_t)(((int64_t)r16 * g.ldc + col) * 2) : kPOff;
-  const uint32_t aoff = ok ? (uint32_t)(((int64_t)r16 * g.ldaux + col) * 2) : kPOff;
+  const uint32_t off = ok ? (uint32_t)(((int64_t)r16 * g.ldc + col) * 2) : kOff;
+  const uint32_t aoff = ok ? (uint32_t)(((int64_t)r16 * g.ldaux + col) * 2) : kOff;
   float csum[8];
 #pragma unroll
   for (int e2 = 0; e2 < 8; ++e2) csum[e2] = 0.f;
@@ -516,7 +498,7 @@ PL_DEV void pp_epi_quad(f32x4 (&acc)[4][8], const PPCtx& c, const PPEpi& e, cons
       asm volatile("" : "+v"(lo));
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] = fmaxf(v[q] + bias[q], lo);
-      pp_st16(crs, off, pack8(v));
+      bst16(crs, off, pack8(v));
     } else if constexpr (EPI == 1) {
       float lo = -INFINITY;  // (as EPI 0)
       asm volatile("" : "+v"(lo));
@@ -527,12 +509,12 @@ PL_DEV void pp_epi_quad(f32x4 (&acc)[4][8], const PPCtx& c, const PPEpi& e, cons
       unpack8(pre, f);  // the activation reads the bf16-rounded pre-activation
 #pragma unroll
       for (int q = 0; q < 8; ++q) f[q] = gelu_f(f[q]);
-      pp_st16(ars, aoff, pre);
-      pp_st16(crs, off, pack8(f));
+      bst16(ars, aoff, pre);
+      bst16(crs, off, pack8(f));
     } else if constexpr (EPI == 2) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] = fmaxf(v[q] + bias[q], 0.f);
-      pp_st16(crs, off, pack8(v));
+      bst16(crs, off, pack8(v));
     } else if constexpr (EPI == 3 || EPI == 4) {
       float a[8];
       unpack8(ax[jj], a);
@@ -542,13 +524,13 @@ PL_DEV void pp_epi_quad(f32x4 (&acc)[4][8], const PPCtx& c, const PPEpi& e, cons
         v[q] = EPI == 3 ? d * gelu_df(a[q]) : (a[q] > 0.f ? d : 0.f);
       }
       const u32x4 o = pack8(v);
-      pp_st16(crs, off, o);
+      bst16(crs, off, o);
       unpack8(o, v);  // the bias gradient sums the bf16-rounded values, like act_bwd_colsum
 #pragma unroll
       for (int q = 0; q < 8; ++q) csum[q] += v[q];
     } else {  // EPI 6: dO stored; delta = sum over the wave's 64 columns (one head) of dO * O
       const u32x4 o = pack8(v);
-      pp_st16(crs, off, o);
+      bst16(crs, off, o);
       float d[8], oo[8];
       unpack8(o, d);
       unpack8(ax[jj], oo);
@@ -572,9 +554,9 @@ PL_DEV void pp_epi_quad(f32x4 (&acc)[4][8], const PPCtx& c, const PPEpi& e, cons
     }
     const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(g.colpart + (int64_t)(4 * e.tm + 2 * c.wr + jh) * N), (short)0, e.valid ? N * 4 : 0, 0x00020000);
-    const uint32_t po = (ok && r16 == 0) ? (uint32_t)col * 4u : kPOff;
-    pp_st16(prs, po, __builtin_bit_cast(u32x4, f32x4{csum[0], csum[1], csum[2], csum[3]}));
-    pp_st16(prs, po == kPOff ? kPOff : po + 16u, __builtin_bit_cast(u32x4, f32x4{csum[4], csum[5], csum[6], csum[7]}));
+    const uint32_t po = (ok && r16 == 0) ? (uint32_t)col * 4u : kOff;
+    bst16(prs, po, __builtin_bit_cast(u32x4, f32x4{csum[0], csum[1], csum[2], csum[3]}));
+    bst16(prs, po == kOff ? kOff : po + 16u, __builtin_bit_cast(u32x4, f32x4{csum[4], csum[5], csum[6], csum[7]}));
   }
   if constexpr (EPI == 6 && !first_of_half) {
     const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc(
@@ -591,7 +573,7 @@ PL_DEV void pp_epi_quad(f32x4 (&acc)[4][8], const PPCtx& c, const PPEpi& e, cons
       const int mb = m0 + c.wr * 128 + 16 * (4 * jh + jj);
       const int bq = mb / g.T, tq0 = mb - bq * g.T, hd = (n0 + c.wc * 64) >> 6;
       const uint32_t doff = (g4 == 0 && mb + r16 < M && (n0 + c.wc * 64) < N)
-                                ? (uint32_t)((((int64_t)bq * (N >> 6) + hd) * g.T + tq0 + r16) * 4) : kPOff;
+                                ? (uint32_t)((((int64_t)bq * (N >> 6) + hd) * g.T + tq0 + r16) * 4) : kOff;
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, sum), drs, doff, 0, 0);
     }
   }
@@ -668,7 +650,7 @@ PL_DEV void pp_phase(const PPCtx& c, f32x4 (&acc)[4][8], bf16x8 (&fa)[2][4], bf1
       for (int k = 0; k < 2; ++k)
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj)
-          fa[k][jj] = ldsf(reinterpret_cast<const uint16_t*>(
+          fa[k][jj] = lds_frag(reinterpret_cast<const uint16_t*>(
               sb + c.rdA[k] + (unsigned)((wr * 128 + 16 * (4 * jh + jj)) * PBK * 2)));
     }
     if constexpr (PH != 2) {
@@ -677,7 +659,7 @@ PL_DEV void pp_phase(const PPCtx& c, f32x4 (&acc)[4][8], bf16x8 (&fa)[2][4], bf1
       for (int k = 0; k < 2; ++k)
 #pragma unroll
         for (int ii = 0; ii < 2; ++ii)
-          fb[k][ii] = ldsf(reinterpret_cast<const uint16_t*>(
+          fb[k][ii] = lds_frag(reinterpret_cast<const uint16_t*>(
               sb + c.rdB[k] + (unsigned)((PIMG + (wc * 64 + 16 * (2 * p + ii)) * PBK) * 2)));
     }
   }
@@ -781,7 +763,7 @@ __global__ __launch_bounds__(PNT) void gemm_pp_kernel(pllm::GemmArgs g) {
   int tm, tn;
   // prologue: the first segment's first K-tile, all four piece groups, fully landed
   {
-    pp_tile(lid, tiles_m, tiles_n, g.group_m, tm, tn);
+    tile_of(lid, tiles_m, tiles_n, g.group_m, tm, tn);
     const PPSrd srd = pp_srds<EPI>(c, tm, tn, 0, true);
     pp_issue<0, EPI>(c, srd, 0);
     pp_issue<1, EPI>(c, srd, 0);
@@ -799,11 +781,11 @@ __global__ __launch_bounds__(PNT) void gemm_pp_kernel(pllm::GemmArgs g) {
   int s = 0;
   PPEpi pe{tm, tn, false};  // the previous tile (none yet)
   for (int i = 0; i < R; ++i) {
-    pp_tile(lid + i * G, tiles_m, tiles_n, g.group_m, tm, tn);
+    tile_of(lid + i * G, tiles_m, tiles_n, g.group_m, tm, tn);
     const PPEpi ce{tm, tn, true};
     const bool more = i + 1 < R;
     int tm2 = tm, tn2 = tn;
-    if (more) pp_tile(lid + (i + 1) * G, tiles_m, tiles_n, g.group_m, tm2, tn2);
+    if (more) tile_of(lid + (i + 1) * G, tiles_m, tiles_n, g.group_m, tm2, tn2);
     // K-tile kt's DMA carries K-tile kt + 1, or the next segment's first K-tile after the last one.
     // The first K-tile is peeled: its MFMAs start the accumulators from zero (with quadrant
     // epilogues: each quadrant right after that quadrant's epilogue of the previous tile).

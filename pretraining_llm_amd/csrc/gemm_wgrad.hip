@@ -1,7 +1,7 @@
 // Weight-gradient GEMM for linear layers on gfx950 MFMA (the one-barrier kernel; since round 4 the
 // default for fp32 gradient targets is the ping-pong kernel of wgrad_pp.hip, dispatched from wgrad()
 // below with the same split-K plan, slab layout and reduce; this kernel serves bf16 targets and
-// wgrad_set_mfma(100 / 16 / 32 / 1xx) A/B runs):
+// wgrad_set_mfma(100 / 16 / 32) A/B runs):
 //     dW[P, Q] (+)= sum_m dY[m, P] * X[m, Q]          (bf16 in, fp32 accumulate)
 // i.e. the reduction runs over the token dimension (M = batch*seq, 65536 for the
 // headline config) while the output is small (768x768 .. 50304x768).  Both operands
@@ -41,9 +41,6 @@
 //    192 KiB of LDS reads per stage (profiles/r2_wgrad_4wave_negative.jsonl) -- LDS read volume is not
 //    the limiter; the second wave per SIMD covering the per-stage barrier / DMA latency is worth more.
 // Requires M % 64 == 0 and P, Q multiples of 8 (checked by the host binding).
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -55,23 +52,6 @@
 // symmetric (every wave loading) DMA plan (1-8 % slower than the asymmetric one, r3_wgrad_asym_ab.md).
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-PL_DEV f32x16 mfma32(const bf16x8& a, const bf16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-PL_DEV f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-PL_DEV s16x4 ds_tr(const uint16_t* p) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p); }
-PL_DEV bf16x8 cat_tr(const s16x4& lo, const s16x4& hi) {
-  s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-// buffer-descriptor form (srd_of / blds16): common.h
-PL_DEV int acc_row(int i, int half) { return (i & 3) + 8 * (i >> 2) + 4 * half; }
 
 // [rows][128] bf16 image, 16-B chunk ch of row r at ch ^ f(r) (conflict-free tr reads)
 PL_DEV int swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
@@ -327,21 +307,15 @@ namespace pllm {
 
 // Variant selection (wgrad_set_mfma): 0 = default -- the ping-pong kernel of wgrad_pp.hip where it
 // applies (fp32 gradient target), else this file's kernel per shape; 100 = this file's kernel per
-// shape; 116 / 132 (or 16 / 32) = this file's kernel with that MFMA shape.
-// Same-box A/B of this file's variants (profiles/r3_wgrad_asym_ab.md): the asymmetric DMA is +1-8 %
-// over the symmetric kernel; 16x16x32 wins everywhere except the LM-head shapes (P = vocabulary),
-// where 32x32x16 does (+0.5-4 %)
-static int g_wgrad_mfma = 0;
+// shape (as does any other non-zero value); 16 / 32 = this file's kernel with that MFMA shape.
+// Same-box A/B of the MFMA shapes (profiles/r3_wgrad_asym_ab.md): 16x16x32 wins everywhere except the
+// LM-head shapes (P = vocabulary), where 32x32x16 does (+0.5-4 %)
+static int g_wgrad_mfma = 0;  // 0: per shape
 static bool g_wgrad_pp = true;
 void wgrad_set_mfma(int mf) {
   g_wgrad_pp = mf == 0;
-  const int v = mf % 100;
-  g_wgrad_mfma = v == 0 ? 0 : (v == 16 ? 16 : 32);
+  g_wgrad_mfma = (mf == 16 || mf == 32) ? mf : 0;
 }
-
-// A/B switch for slice-count sweeps (bench/wgrad_slices.py): > 0 forces that many slices
-static int g_wgrad_force_s = 0;
-void wgrad_force_slices(int s) { g_wgrad_force_s = s > 0 ? s : 0; }
 
 void wgrad_plan(int M, int P, int Q, int* S, int* slice) {
   // Split-K slice count from a cost model: rounds of 256 workgroups (one per CU) x stages per
@@ -365,7 +339,6 @@ void wgrad_plan(int M, int P, int Q, int* S, int* slice) {
       best = s;
     }
   }
-  if (g_wgrad_force_s > 0) best = std::min(g_wgrad_force_s, std::max(1, kst));
   int st_per = (kst + best - 1) / best;
   *slice = st_per * BKM;
   *S = (kst + st_per - 1) / st_per;

@@ -40,7 +40,7 @@ struct AttnBwdArgs {
   float* dq_sum;  // [B, T, H, D] fp32 running dQ sum across passes (null when one pass)
   int kb0, nkb_pass;  // first key block of the pass / key blocks per pass (set by the host)
   int64_t slab;       // elements per dQ slab (>= B * ceil32(T) * H * D)
-  int nqt;            // ceil(T / 32): query tiles per head in the fragment-order slab (RS kernel)
+  int nqt;            // ceil(T / 32): query tiles per head in the fragment-order slab
   uint16_t *dq, *dk, *dv;
   int B, H, Hkv, T, S, D;
   int64_t q_sb, q_st, q_sh, k_sb, k_st, k_sh, v_sb, v_st, v_sh, o_sb, o_st, o_sh, do_sb, do_st, do_sh;
@@ -137,8 +137,9 @@ int gemm_colsum_groups(int M, int K);  // column-sum partial rows (epi 3 / 4) of
 bool gemm_uses_pp(int K, int epi, int T);
 // gemm_wgrad.hip: dW[P,Q] (+)= dY[M,P]^T X[M,Q]; part: fp32 [S, P, Q] workspace (wgrad_plan)
 void wgrad_plan(int M, int P, int Q, int* S, int* slice);
+// 0: default dispatch; 16 / 32: gemm_wgrad.hip's kernel with that MFMA shape; any other value (100): that
+// kernel with the MFMA shape chosen per problem
 void wgrad_set_mfma(int mf);
-void wgrad_force_slices(int s);
 // bpart / bout (optional): also the bias gradient db[P] (+)= column sums of dY, through an fp32 [S][P]
 // workspace (S = wgrad_bias_slices); returns whether it was computed (16x16x32 kernel only)
 int wgrad_bias_slices(int M, int P, int Q);
@@ -207,11 +208,8 @@ void gemv(const GemvArgs& a, hipStream_t st);
 
 // attention.hip
 bool attn_supported_head_dim(int D);
-int attn_bwd_key_block(int D);  // keys per backward workgroup = dq_acc slab count divisor
-// attn_bwd_ks.hip: keys per workgroup; one pass of the key-stationary main kernel (AttnBwdArgs as attn_bwd)
-int attn_bwd_ks_key_block();
-
-void attn_bwd_set_ks(int mask);  // A/B: bit 0 = D 64, bit 1 = D 128 on the key-stationary kernel
+constexpr int kAttnBwdKeyBlock = 256;  // keys per backward workgroup = dq_acc slab count divisor
+// attn_bwd_ks.hip: one pass of the key-stationary main kernel, D = 128 (AttnBwdArgs as attn_bwd)
 void attn_bwd_ks_launch(const AttnBwdArgs& a, hipStream_t st);
 // attn_decode.hip: split-KV single-query attention over a KV cache
 bool attn_decode_supported(int D, int group);

@@ -37,26 +37,15 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 constexpr int WT = 256;          // output tile (P and Q)
 constexpr int WBK = 64;          // tokens per K-tile
 constexpr int WNT = 512;         // 8 waves
 constexpr int WIMG = WBK * 32;   // elements of one [64][32] image (4 KiB)
 constexpr int WSLOT = 16 * WIMG; // 8 dY images then 8 X images: 64 KiB
-constexpr uint32_t kWOff = 0x80000000u;  // a byte offset past every descriptor built here
 
-PL_DEV f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-PL_DEV s16x4 ds_tr(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(const uint16_t*)p);
-}
-PL_DEV bf16x8 frag_tr(const char* p) {
+PL_DEV bf16x8 frag_tr(const char* p) {  // p: byte address in an image
   // rows r and r + 4 of the image (+256 B): 8 consecutive tokens of the lane's column
-  const s16x4 lo = ds_tr(p), hi = ds_tr(p + 256);
-  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+  return cat_tr(ds_tr(reinterpret_cast<const uint16_t*>(p)), ds_tr(reinterpret_cast<const uint16_t*>(p + 256)));
 }
 PL_DEV void wp_barrier() {
   __builtin_amdgcn_sched_barrier(0);
@@ -316,7 +305,7 @@ PL_DEV void wp_epilogue(const WPCtx& c, f32x4 (&acc)[4][8], const WPSeg& sg) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int q = col0 + c.wc * 64 + 16 * t + 4 * g4;
-      off[t] = q < cols_lim ? (uint32_t)(r16 * ld + q) * 4u : kWOff;
+      off[t] = q < cols_lim ? (uint32_t)(r16 * ld + q) * 4u : kOff;
     }
     if (rmw) {
 #pragma unroll
@@ -412,7 +401,7 @@ __global__ __launch_bounds__(WNT) void wgrad_pp_kernel(WPArgs g) {
 #pragma unroll
         for (int jh = 0; jh < 2; ++jh) {
           const int prow = sg.tp * WT + c.wr * 128 + 16 * (4 * jh + c.wc) + lane;
-          const uint32_t bo = ((lane >> 4) == 0 && prow < g.P) ? (uint32_t)prow * 4u : kWOff;
+          const uint32_t bo = ((lane >> 4) == 0 && prow < g.P) ? (uint32_t)prow * 4u : kOff;
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, bacc[jh][0]), brs, bo, 0, 0);
         }
       }

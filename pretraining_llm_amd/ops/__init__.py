@@ -257,7 +257,7 @@ def linear(x, weight, bias=None, bias_grad_external: bool = False, residual=None
 def gemm_config(reserve_cus: Optional[int] = None, persistent: Optional[bool] = None) -> bool:
     """Configure the hand-written fused-epilogue TN GEMM (``torch.ops.pllm.gemm_tn``: the ping-pong main loop of
     csrc/gemm_pp.hip; shapes it does not take -- K < 128, the delta epilogue with T % 16 != 0 -- fall back to the
-    round-3 persistent loop of csrc/gemm.hip): ``reserve_cus``: CUs its persistent grid leaves free (RCCL
+    one-barrier persistent loop of csrc/gemm.hip): ``reserve_cus``: CUs its persistent grid leaves free (RCCL
     kernels run beside the backward at world > 1); ``persistent`` False: the ping-pong GEMM and weight-gradient
     kernels launch one workgroup per tile / work item instead of one per CU, so a CU held by a concurrent RCCL
     kernel delays no tile list (the hardware deals the tiles to the free CUs).  None keeps the current
@@ -270,8 +270,8 @@ def gemm_config(reserve_cus: Optional[int] = None, persistent: Optional[bool] = 
 
 
 # PLLM_FUSED_MLP: "bwd" (default) = forward on hipBLASLt + the activation kernel, backward through
-# the fused data-gradient epilogue (act' + b1's gradient: 476-480 vs 512 us per GPT-2 layer, bench/
-# gemm_tn_bench.py); "all" = the forward activation in the GEMM epilogue too (its main loop is
+# the fused data-gradient epilogue (act' + b1's gradient: 476-480 vs 512 us per GPT-2 layer, measured in
+# round 3); "all" = the forward activation in the GEMM epilogue too (its main loop is
 # still slower than hipBLASLt's: 423-440 vs 408 us with the separate GELU pass); "0" = neither
 _FM = _os.environ.get("PLLM_FUSED_MLP", "bwd")
 FUSED_MLP = _FM in ("1", "all", "bwd")

@@ -602,9 +602,9 @@ def test_wgrad_kernel(M, P, Q):
     ref3 = acc32.double() + dy.double().t() @ x.double()
     torch.ops.pllm.wgrad(dy, x, acc32)
     assert _rel(acc32.double(), ref3) < 1e-5, _rel(acc32.double(), ref3)
-    # the 16x16x32 MFMA variant computes the same product
+    # the one-barrier kernel (csrc/gemm_wgrad.hip) with either MFMA shape computes the same product
     try:
-        for variant in (16, 32, 116, 132):  # 1xx: the asymmetric-DMA variant
+        for variant in (16, 32):
             torch.ops.pllm.wgrad_set_mfma(variant)
             assert _rel(torch.ops.pllm.wgrad(dy, x), ref) < 5e-3, variant
             acc32 = torch.randn(P, Q, device=DEV)
@@ -634,7 +634,7 @@ def test_wgrad_fused_bias_grad(M, P, Q, bias_f32):
     x = torch.randn(M, Q, device=DEV).bfloat16()
     w0 = torch.randn(P, Q, device=DEV)
     try:
-        for variant in (0, 16, 116, 132):
+        for variant in (0, 16, 32):
             torch.ops.pllm.wgrad_set_mfma(variant)
             b0 = torch.randn(P, device=DEV)
             b0 = b0 if bias_f32 else b0.bfloat16()
@@ -1133,11 +1133,11 @@ def test_lse_merge_kernel(D):
                                                  (512, 512, 2, 1, 2, False), (320, 384, 2, 2, 1, True),
                                                  (300, 340, 2, 1, 1, True), (96, 700, 2, 2, 1, False)])
 def test_attention_bwd_key_stationary(D, T, S, H, Hkv, B, causal):
-    """The key-stationary backward (csrc/attn_bwd_ks.hip: 4 waves x 64 keys, dK / dV in the accumulator
-    file, one barrier per query slice) vs fp32 math and vs the previous kernels (fused-role D = 64,
-    role-split D = 128): causal and not, GQA, ragged T, queries aligned to the END of longer key rows
-    (S > T, offset 64 = 32-aligned and 40 = the per-element masked path), ragged key blocks (S = 340, 700),
-    and a forced one-key-block-per-pass run (bit-identical)."""
+    """The backward that ships for each head dim -- D = 128: the key-stationary kernel (csrc/attn_bwd_ks.hip:
+    4 waves x 64 keys, dK / dV in the accumulator file, one barrier per query slice); D = 64: the fused-role
+    kernel (csrc/attention.hip) -- vs fp32 math: causal and not, GQA, ragged T, queries aligned to the END of
+    longer key rows (S > T, offset 64 = 32-aligned and 40 = the per-element masked path), ragged key blocks
+    (S = 340, 700), and a forced one-key-block-per-pass run (bit-identical)."""
     torch.manual_seed(T + S + D)
     q = torch.randn(B, T, H, D, device=DEV).bfloat16()
     k = torch.randn(B, S, Hkv, D, device=DEV).bfloat16()
@@ -1149,7 +1149,6 @@ def test_attention_bwd_key_stationary(D, T, S, H, Hkv, B, causal):
     of, _ = _attn_ref(qf, kf, vf, causal, scale)
     of.backward(do.float())
     try:
-        torch.ops.pllm.attn_bwd_set_ks(3)
         got = [torch.empty_like(t) for t in (q, k, v)]
         torch.ops.pllm.attn_bwd(do, q, k, v, o, lse, *got, causal, scale)
         for a, b, n in zip(got, (qf.grad, kf.grad, vf.grad), ("dq", "dk", "dv")):
@@ -1160,15 +1159,8 @@ def test_attention_bwd_key_stationary(D, T, S, H, Hkv, B, causal):
         torch.ops.pllm.attn_bwd(do, q, k, v, o, lse, *got2, causal, scale)
         for a, b in zip(got2, got):
             assert torch.equal(a, b)
-        torch.ops.pllm.attn_bwd_set_workspace_mb(4096)
-        torch.ops.pllm.attn_bwd_set_ks(0)
-        old = [torch.empty_like(t) for t in (q, k, v)]
-        torch.ops.pllm.attn_bwd(do, q, k, v, o, lse, *old, causal, scale)
-        for a, b, n in zip(got, old, ("dq", "dk", "dv")):
-            assert _rel(a, b) < 1e-2, (n, _rel(a, b))
     finally:
         torch.ops.pllm.attn_bwd_set_workspace_mb(4096)
-        torch.ops.pllm.attn_bwd_set_ks(2)  # the shipped default: D = 128 only
 
 
 @pytest.mark.parametrize("D", [64, 128])
@@ -1176,9 +1168,9 @@ def test_attention_bwd_key_stationary(D, T, S, H, Hkv, B, causal):
 def test_attention_bwd_key_stationary_rope_offset(D, T, S):
     """RoPE with queries aligned to the END of longer key rows (S > T; offsets 64 and 40, the latter not a
     multiple of 32): q is rotated at positions t + S - T and k at s (the rope op), the forward and the
-    backward run on the rotated heads and the backward rotates dq / dk back -- under the key-stationary
-    kernels (mask 3) and under the fused-role D = 64 / role-split D = 128 kernels (mask 0).  Against fp32
-    rotate-half RoPE + causal attention, gradients w.r.t. the UNROTATED q / k."""
+    backward run on the rotated heads and the backward rotates dq / dk back -- under the kernel that ships
+    for the head dim (fused-role D = 64, key-stationary D = 128).  Against fp32 rotate-half RoPE + causal
+    attention, gradients w.r.t. the UNROTATED q / k."""
     from pretraining_llm_amd import ops
     from pretraining_llm_amd.ops import reference as ref
     torch.manual_seed(T + S + D + 5)
@@ -1198,16 +1190,11 @@ def test_attention_bwd_key_stationary_rope_offset(D, T, S):
     krot = torch.ops.pllm.rope(k.view(B, S, Hkv * D), cos, sin, Hkv, Hkv, S, 0, False).view(B, S, Hkv, D)
     o, lse = torch.ops.pllm.attn_fwd(qrot, krot, v, True, scale)
     assert _rel(o, of) < 1.5e-2, _rel(o, of)
-    try:
-        for ks in (3, 0):  # key-stationary at D = 64 and 128 / fused-role D = 64 and role-split D = 128
-            torch.ops.pllm.attn_bwd_set_ks(ks)
-            got = [torch.empty_like(t) for t in (q, k, v)]
-            torch.ops.pllm.attn_bwd(do, qrot, krot, v, o, lse, *got, True, scale, cos, sin)
-            for a, b, n in zip(got, (qf.grad, kf.grad, vf.grad), ("dq", "dk", "dv")):
-                assert not a.isnan().any(), (ks, n)
-                assert _rel(a, b) < 3e-2, (ks, n, _rel(a, b))
-    finally:
-        torch.ops.pllm.attn_bwd_set_ks(2)  # the shipped default: D = 128 only
+    got = [torch.empty_like(t) for t in (q, k, v)]
+    torch.ops.pllm.attn_bwd(do, qrot, krot, v, o, lse, *got, True, scale, cos, sin)
+    for a, b, n in zip(got, (qf.grad, kf.grad, vf.grad), ("dq", "dk", "dv")):
+        assert not a.isnan().any(), n
+        assert _rel(a, b) < 3e-2, (n, _rel(a, b))
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
