@@ -92,6 +92,8 @@ default_config = {
     'gemm_persistent': 'auto',        # persistent ping-pong GEMM grids: auto = world 1 only (train/graph.py)
     'graph_collectives': False,       # refused (eager step): capturing RCCL collectives aborts (train/graph.py)
     'activation_checkpointing': None,
+    'qk_norm': None,                  # True: RMSNorm over head_dim of every q / k head before RoPE (None -> the preset's)
+    'qk_norm_eps': None,
     'override_preset_dims': False,    # with model_preset: the dims above (n_embed, n_head, n_blocks, ...) override the preset's
     'tuned_gemms': True,              # GPU: load the shipped TunableOp GEMM selections (pretraining_llm_amd/tuning/)
     'tp_size': 1,                     # tensor parallelism: heads / FFN columns sharded (parallel/model_parallel.py)

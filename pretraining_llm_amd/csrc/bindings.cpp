@@ -525,6 +525,91 @@ Tensor rope(const Tensor& x, const Tensor& cos, const Tensor& sin, int64_t n_hea
   return out;
 }
 
+// QK-norm pre-pass of the attention (csrc/qk_norm.hip): per-head RMSNorm of the q / k heads of packed qkv
+// [.., (H + 2 Hkv) D] with gains wq / wk [D], then RoPE when tables are given -> (qk [.., (H + Hkv) D] in
+// rope_qk's layout, rstd fp32 [rows, H + Hkv])
+int64_t check_qk_norm(const Tensor& qkv, const Tensor& wq, const Tensor& wk, int64_t H, int64_t Hkv, const char* op) {
+  check_bf16(qkv, "qkv");
+  check_contig(qkv, "qkv");
+  check_aligned16(qkv, "qkv");
+  check_bf16(wq, "wq");
+  check_bf16(wk, "wk");
+  TORCH_CHECK(qkv.dim() >= 2 && H > 0 && Hkv > 0 && qkv.size(-1) % (H + 2 * Hkv) == 0, op, ": heads");
+  const int64_t D = qkv.size(-1) / (H + 2 * Hkv);
+  TORCH_CHECK(D % 16 == 0 && (D == 32 || D == 64 || D == 128), op, ": head dim must be 32, 64 or 128, got ", D);
+  TORCH_CHECK(wq.numel() == D && wk.numel() == D && wq.is_contiguous() && wk.is_contiguous(), op, ": gain shape [D]");
+  check_aligned16(wq, "wq");
+  check_aligned16(wk, "wk");
+  return D;
+}
+
+std::tuple<Tensor, Tensor> qk_norm_rope(const Tensor& qkv, const Tensor& wq, const Tensor& wk, double eps, int64_t H,
+                                        int64_t Hkv, const std::optional<Tensor>& cos,
+                                        const std::optional<Tensor>& sin, int64_t T, int64_t pos_offset) {
+  const int64_t D = check_qk_norm(qkv, wq, wk, H, Hkv, "qk_norm_rope");
+  const int64_t W = qkv.size(-1), rows = qkv.numel() / W;
+  TORCH_CHECK(cos.has_value() == sin.has_value(), "qk_norm_rope: cos and sin go together");
+  TORCH_CHECK(T > 0 && rows % T == 0, "qk_norm_rope: rows must be a multiple of T");
+  TORCH_CHECK(pos_offset >= 0, "qk_norm_rope: pos_offset");
+  if (cos) {
+    for (const Tensor* t : {&*cos, &*sin}) {
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->dim() == 2,
+                  "qk_norm_rope: rope tables must be contiguous fp32 [positions, D/2] GPU tensors");
+      TORCH_CHECK(t->size(1) == D / 2 && t->size(0) >= T + pos_offset, "qk_norm_rope: table shape");
+      check_aligned16(*t, "rope table");
+    }
+  }
+  auto sizes = qkv.sizes().vec();
+  sizes.back() = (H + Hkv) * D;
+  Tensor qk = at::empty(sizes, qkv.options());
+  Tensor rstd = at::empty({rows, H + Hkv}, qkv.options().dtype(at::kFloat));
+  if (rows)
+    pllm::qk_norm_rope(qkv.data_ptr(), wq.data_ptr(), wk.data_ptr(), qk.data_ptr(), rstd.data_ptr<float>(),
+                       cos ? cos->data_ptr<float>() : nullptr, sin ? sin->data_ptr<float>() : nullptr, (size_t)rows,
+                       (int)T, (int)H, (int)Hkv, (int)D, (int)pos_offset, (float)eps, cur_stream());
+  return {qk, rstd};
+}
+
+// QK-norm backward, in place on the q / k columns of the packed dqkv (dy -> dx; the v columns are not touched).
+// dwq_acc / dwk_acc: the gain gradients are added into (or, overwrite, stored to) these and empty tensors come
+// back; without them fresh bf16 [D] gradients are returned.
+std::tuple<Tensor, Tensor> qk_norm_bwd_(Tensor& dqkv, const Tensor& qkv, const Tensor& rstd, const Tensor& wq,
+                                        const Tensor& wk, int64_t H, int64_t Hkv,
+                                        const std::optional<Tensor>& dwq_acc, const std::optional<Tensor>& dwk_acc,
+                                        bool overwrite) {
+  const int64_t D = check_qk_norm(qkv, wq, wk, H, Hkv, "qk_norm_bwd_");
+  const int64_t W = qkv.size(-1), rows = qkv.numel() / W;
+  check_bf16(dqkv, "dqkv");
+  check_contig(dqkv, "dqkv");
+  check_aligned16(dqkv, "dqkv");
+  TORCH_CHECK(dqkv.sizes() == qkv.sizes(), "qk_norm_bwd_: dqkv shape");
+  TORCH_CHECK(rstd.is_cuda() && rstd.scalar_type() == at::kFloat && rstd.is_contiguous() &&
+                  rstd.numel() == rows * (H + Hkv), "qk_norm_bwd_: rstd must be fp32 [rows, H + Hkv]");
+  const bool acc = dwq_acc.has_value();
+  TORCH_CHECK(acc == dwk_acc.has_value(), "qk_norm_bwd_: dwq_acc and dwk_acc go together");
+  bool gf32 = false;
+  if (acc) {
+    gf32 = check_grad(*dwq_acc, "dwq_acc");
+    TORCH_CHECK(check_grad(*dwk_acc, "dwk_acc") == gf32, "dwk_acc dtype must match dwq_acc");
+    TORCH_CHECK(dwq_acc->numel() == D && dwk_acc->numel() == D && dwq_acc->is_contiguous() && dwk_acc->is_contiguous(),
+                "qk_norm_bwd_: accumulate target shape [D]");
+  }
+  Tensor dwq = acc ? *dwq_acc : at::zeros({D}, wq.options());
+  Tensor dwk = acc ? *dwk_acc : at::zeros({D}, wk.options());
+  if (rows) {
+    const int G = pllm::qk_norm_bwd_grid((size_t)rows, (int)H, (int)Hkv, (int)D);
+    Tensor part = at::empty({2, G, D}, qkv.options().dtype(at::kFloat));
+    pllm::qk_norm_bwd(dqkv.data_ptr(), qkv.data_ptr(), rstd.data_ptr<float>(), wq.data_ptr(), wk.data_ptr(),
+                      (size_t)rows, (int)H, (int)Hkv, (int)D, part.data_ptr<float>(), dwq.data_ptr(), dwk.data_ptr(),
+                      gf32, acc && !overwrite, cur_stream());
+  } else if (acc && overwrite) {
+    dwq.zero_();
+    dwk.zero_();
+  }
+  if (acc) return {at::empty({0}, wq.options()), at::empty({0}, wk.options())};
+  return {dwq, dwk};
+}
+
 // x *= s in place (x bf16 or fp32, contiguous; s a 1-element fp32 GPU tensor); no pass at all when s == 1
 void scale_(Tensor& x, const Tensor& s) {
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat, "scale_: x bf16 or fp32");
@@ -1097,6 +1182,8 @@ TORCH_LIBRARY(pllm, m) {
   m.def("swiglu_bwd(Tensor dy, Tensor gate_up) -> Tensor");
   m.def("rope(Tensor x, Tensor cos, Tensor sin, int n_heads_total, int n_rot, int T, int pos_offset, bool inverse) -> Tensor");
   m.def("rope_qk(Tensor x, Tensor cos, Tensor sin, int n_heads_total, int n_rot, int T) -> Tensor");
+  m.def("qk_norm_rope(Tensor qkv, Tensor wq, Tensor wk, float eps, int n_head, int n_kv_head, Tensor? cos, Tensor? sin, int T, int pos_offset=0) -> (Tensor qk, Tensor rstd)");
+  m.def("qk_norm_bwd_(Tensor(a!) dqkv, Tensor qkv, Tensor rstd, Tensor wq, Tensor wk, int n_head, int n_kv_head, Tensor(b!)? dwq_acc, Tensor(c!)? dwk_acc, bool overwrite) -> (Tensor dwq, Tensor dwk)");
   m.def("scale_(Tensor(a!) x, Tensor s) -> ()");
   m.def("lse_merge_(Tensor(a!) o_acc, Tensor(b!) lse_acc, Tensor o, Tensor lse) -> ()");
   m.def("zero_ranges_(Tensor(a!) buf, Tensor ranges, int total_len) -> ()");
@@ -1131,6 +1218,8 @@ TORCH_LIBRARY_IMPL(pllm, CUDA, m) {
   m.impl("swiglu_bwd", swiglu_bwd);
   m.impl("rope", rope);
   m.impl("rope_qk", rope_qk);
+  m.impl("qk_norm_rope", qk_norm_rope);
+  m.impl("qk_norm_bwd_", qk_norm_bwd_);
   m.impl("scale_", scale_);
   m.impl("lse_merge_", lse_merge_);
   m.impl("zero_ranges_", zero_ranges_);

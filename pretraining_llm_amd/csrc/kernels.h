@@ -87,6 +87,17 @@ void zero_ranges(void* buf, const int64_t* desc, int n, int64_t total_bytes, hip
 void lse_merge(float* o_acc, float* lse_acc, const void* o, const float* lse, const int64_t* st, int B, int T, int H,
                int D, hipStream_t stream);
 
+// qk_norm.hip: per-head RMSNorm of the q / k heads of packed qkv rows [rows, (H + 2 Hkv) D], fused into the
+// attention's RoPE pre-pass.  Forward: qk [rows, (H + Hkv) D] = rotate(x rstd gamma) (no rotation when cosb is
+// null), rstd fp32 [rows, H + Hkv].  Backward: in place on the q / k columns of dqkv (dy -> dx), the gain
+// gradients through fp32 partials part [2][qk_norm_bwd_grid()][D] and col_reduce (deterministic).
+void qk_norm_rope(const void* qkv, const void* wq, const void* wk, void* qk, float* rstd, const float* cosb,
+                  const float* sinb, size_t rows, int T, int H, int Hkv, int D, int pos_offset, float eps,
+                  hipStream_t st);
+int qk_norm_bwd_grid(size_t rows, int H, int Hkv, int D);
+void qk_norm_bwd(void* dqkv, const void* qkv, const float* rstd, const void* wq, const void* wk, size_t rows, int H,
+                 int Hkv, int D, float* part, void* dwq, void* dwk, bool grad_f32, bool accumulate, hipStream_t st);
+
 // cross_entropy.hip
 void cross_entropy(const void* logits, int64_t ld, const int64_t* targets, int N, int V, int ignore_index,
                    float* loss, void* dlogits, const float* inv_n, hipStream_t st);

@@ -40,7 +40,11 @@ class ModelConfig:
     head_bias: bool = False                  # bias on lm_head (reference: True)
     norm_eps: float = 1e-5
     rope_theta: float = 10000.0
-    init: str = "gpt2"                       # gpt2 | torch_default
+    # QK-norm (OLMo-2 / Qwen-3 / Gemma-3): RMSNorm over the head dimension of every q and k head, one
+    # gain vector of head_dim each per block, after the QKV projection and before RoPE
+    qk_norm: bool = False
+    qk_norm_eps: float = 1e-5
+    init: str = "gpt2"                      # gpt2 | torch_default
     init_std: float = 0.02
     # True / False, a float fraction of the blocks, or "auto": checkpoint only as many blocks as
     # it takes for a step's activations to fit comfortably in the free HBM (GPT.checkpointed_blocks)
@@ -52,6 +56,9 @@ class ModelConfig:
             self.n_kv_head = self.n_head
         assert self.n_embed % self.n_head == 0, "n_embed must be divisible by n_head"
         assert self.n_head % self.n_kv_head == 0, "n_head must be divisible by n_kv_head"
+        if self.qk_norm and self.arch == "ref":
+            raise ValueError("qk_norm is not available with arch='ref': the reference checkpoint layout "
+                             "(per-head key / query / value weights) has no place for the gains")
         if self.ffn_hidden is None:
             if self.mlp == "swiglu":
                 h = int(2 * (4 * self.n_embed) / 3)
@@ -103,6 +110,8 @@ class ModelConfig:
             per += 2 * C * F + b * (F + C)
         nparam_norm = 2 * C if self.norm == "layernorm" else C
         per += 2 * nparam_norm
+        if self.qk_norm:
+            per += 2 * self.head_dim
         n = L * per + nparam_norm
         emb = V * C + (T * C if self.pos == "learned" else 0)
         if include_embedding:
@@ -170,6 +179,11 @@ PRESETS = {
                                  ffn_hidden=5504),
     "llama-tiny": lambda: _llama(vocab_size=512, context_length=128, n_embed=128, n_head=4, n_blocks=2,
                                  n_kv_head=2, ffn_hidden=256),
+    # the same two with QK-norm
+    "llama-1.3b-qknorm": lambda: _llama(vocab_size=50304, context_length=2048, n_embed=2048, n_head=16, n_blocks=24,
+                                        ffn_hidden=5504, qk_norm=True),
+    "llama-tiny-qknorm": lambda: _llama(vocab_size=512, context_length=128, n_embed=128, n_head=4, n_blocks=2,
+                                        n_kv_head=2, ffn_hidden=256, qk_norm=True),
 }
 
 

@@ -60,6 +60,15 @@ class Norm(nn.Module):
         return ops.norm_linear(x, residual, self.weight, self.bias, self.eps, self.rms, weight, bias, act, kv)
 
 
+class HeadNorm(nn.Module):
+    """The gain vector of a QK-norm (one per block for q, one for k); the norm itself runs inside the
+    attention's pre-pass (ops.attention_packed / ops.qk_norm_packed)."""
+
+    def __init__(self, head_dim: int):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(head_dim))
+
+
 class Attention(nn.Module):
     def __init__(self, cfg: ModelConfig, layer_idx: int = 0):
         super().__init__()
@@ -69,6 +78,15 @@ class Attention(nn.Module):
         qkv_out = (cfg.n_head + 2 * cfg.n_kv_head) * cfg.head_dim
         self.qkv = nn.Linear(C, qkv_out, bias=cfg.bias and cfg.arch != "ref")
         self.proj = nn.Linear(C, C, bias=cfg.bias) if cfg.attn_out_proj else None
+        self.qk_norm = bool(cfg.qk_norm)
+        if self.qk_norm:  # only then: state dicts of models without QK-norm keep their keys
+            self.q_norm, self.k_norm = HeadNorm(cfg.head_dim), HeadNorm(cfg.head_dim)
+
+    def _qk_norm_kw(self) -> dict:
+        if not self.qk_norm:
+            return {}
+        return dict(q_norm_weight=self.q_norm.weight, k_norm_weight=self.k_norm.weight,
+                    qk_norm_eps=self.cfg.qk_norm_eps)
 
     def forward(self, x, rope=None, fuse_out_bias: bool = False):
         return self.forward_res(x, rope, fuse_out_bias)[0]
@@ -84,8 +102,9 @@ class Attention(nn.Module):
             r = residual if ops.resid_gemm_ok(residual, self.proj.weight) else None
             return ops.attention_proj(qkv, self.n_head, self.n_kv_head, self.proj.weight, self.proj.bias,
                                       rope_cos=cos, rope_sin=sin, bias_grad_external=fuse_out_bias,
-                                      residual=r), r is not None
-        y = ops.attention_packed(qkv, self.n_head, self.n_kv_head, causal=True, rope_cos=cos, rope_sin=sin)
+                                      residual=r, **self._qk_norm_kw()), r is not None
+        y = ops.attention_packed(qkv, self.n_head, self.n_kv_head, causal=True, rope_cos=cos, rope_sin=sin,
+                                 **self._qk_norm_kw())
         if self.proj is not None:
             r = residual if ops.resid_gemm_ok(residual, self.proj.weight) else None
             return ops.linear(y, self.proj.weight, self.proj.bias, bias_grad_external=fuse_out_bias,
@@ -101,7 +120,11 @@ class Attention(nn.Module):
         q = qkv[..., : H * D].view(B, T, H, D)
         k = qkv[..., H * D:(H + Hkv) * D].view(B, T, Hkv, D)
         v = qkv[..., (H + Hkv) * D:].view(B, T, Hkv, D)
-        if rope is not None:
+        if self.qk_norm:  # norm and rotation in one pre-pass
+            cos, sin = rope if rope is not None else (None, None)
+            q, k = ops.qk_norm_packed(qkv, self.q_norm.weight, self.k_norm.weight, self.cfg.qk_norm_eps, H, Hkv,
+                                      cos, sin, pos)
+        elif rope is not None:
             cos, sin = rope
             q = ops.apply_rope(q, cos, sin, pos)
             k = ops.apply_rope(k, cos, sin, pos)
@@ -126,7 +149,15 @@ class Attention(nn.Module):
         k = qkv[..., H * D:(H + Hkv) * D].view(B, 1, Hkv, D)
         v = qkv[..., (H + Hkv) * D:].view(B, 1, Hkv, D)
         per_row = pos_t.numel() > 1  # continuous batching: every sequence at its own position
-        if rope is not None:
+        if self.qk_norm:
+            cos = sin = None
+            if rope is not None:
+                cos, sin = rope[0].index_select(0, pos_t), rope[1].index_select(0, pos_t)
+            # (per-row positions: the batch laid out along the time axis, one table row per sequence)
+            q, k = ops.qk_norm_packed(qkv.reshape(1, B, -1) if per_row else qkv, self.q_norm.weight,
+                                      self.k_norm.weight, self.cfg.qk_norm_eps, H, Hkv, cos, sin, 0)
+            q, k = q.reshape(B, 1, H, D), k.reshape(B, 1, Hkv, D)
+        elif rope is not None:
             cos, sin = rope[0].index_select(0, pos_t), rope[1].index_select(0, pos_t)
             if per_row:  # one table row per sequence: lay the batch out along the time axis
                 q = ops.apply_rope(q.reshape(1, B, H, D), cos, sin, 0).view(B, 1, H, D)
@@ -258,9 +289,10 @@ class Block(nn.Module):
         return self._mlp_infer(a, res)
 
     def forward_decode(self, x, residual, cache, layer_idx, pos_t, len_t, rope=None):
-        # without RoPE the QKV projection's epilogue also appends k/v to the cache
+        # without RoPE the QKV projection's epilogue also appends k/v to the cache (not with QK-norm: k is
+        # normalised before it is cached)
         kv = None
-        if rope is None:
+        if rope is None and not getattr(self.attn, "qk_norm", False):
             kv = (cache.k[layer_idx], cache.v[layer_idx], pos_t, self.attn.n_head * self.attn.head_dim)
         qkv, res = self.ln1.linear(x, residual, self.attn.qkv.weight, self.attn.qkv.bias, kv=kv)
         a = self.attn.forward_decode(None, cache, layer_idx, pos_t, len_t, rope, qkv=qkv,
@@ -348,7 +380,7 @@ class GPT(nn.Module):
         between checkpointed and full runs of GPT-2 medium at 32K tokens (36.9 vs 14.4 GB)."""
         cfg = self.config
         per = 6 * cfg.n_embed + 2 * cfg.ffn_hidden
-        if cfg.pos == "rope":  # rotated q / k of the attention pre-pass (ops._FlashAttnPacked)
+        if cfg.pos == "rope" or cfg.qk_norm:  # q / k of the attention pre-pass (ops._FlashAttnPacked)
             per += (cfg.n_head + cfg.n_kv_head) * cfg.head_dim
         return 2 * per * tokens * cfg.n_blocks
 

@@ -667,27 +667,55 @@ def _qkv_heads(qkv, qk, H, Hkv, D):
     return q, k, v
 
 
-def _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin):
-    """Forward attention over packed qkv -> (qk, o, lse); ``qk`` is the rotated q / k buffer of the
-    RoPE pre-pass ([B, T, (H + Hkv) D], None without RoPE), which the backward reads again."""
+def _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, qkn=None):
+    """Forward attention over packed qkv -> (qk, o, lse, rstd); ``qk`` is the q / k buffer of the
+    pre-pass ([B, T, (H + Hkv) D], None without one), which the backward reads again: rotated (RoPE,
+    rope_qk) or, with ``qkn`` = (wq, wk, eps) (QK-norm), normalised per head and then rotated when
+    there are tables (qk_norm_rope, which also returns the heads' ``rstd``; else None)."""
     T = qkv.shape[1]
     D = qkv.shape[2] // (H + 2 * Hkv)
-    qk = _ops().rope_qk(qkv, cos, sin, H + 2 * Hkv, H + Hkv, T) if cos is not None else None
+    rstd = None
+    if qkn is not None:
+        qk, rstd = _ops().qk_norm_rope(qkv, qkn[0], qkn[1], qkn[2], H, Hkv, cos, sin, T, 0)
+    else:
+        qk = _ops().rope_qk(qkv, cos, sin, H + 2 * Hkv, H + Hkv, T) if cos is not None else None
     q, k, v = _qkv_heads(qkv, qk, H, Hkv, D)
     o, lse = _ops().attn_fwd(q, k, v, causal, scale)
-    return qk, o, lse
+    return qk, o, lse, rstd
 
 
-def _attn_packed_bwd(do, qkv, qk, o, lse, cfg, cos, sin, delta=None):
+def _qk_norm_bwd(dqkv, qkv, rstd, wq, wk, H, Hkv):
+    """QK-norm backward in place on the q / k columns of ``dqkv`` -> (dwq, dwk): None when the gain
+    gradients went straight into the flat-gradient slots, else fresh tensors."""
+    (tq, fq), (tk, fk) = _set_target(wq), _set_target(wk)
+    if tq is None or tk is None:
+        for p, t, f in ((wq, tq, fq), (wk, tk, fk)):
+            if t is not None and f:  # not written here after all: leave the slot as it was found
+                p._pllm_grad_fresh = True
+        return _ops().qk_norm_bwd_(dqkv, qkv, rstd, wq, wk, H, Hkv, None, None, False)
+    if fq != fk:  # one slot already written this step: zero the other and add into both
+        (tq if fq else tk).zero_()
+    _ops().qk_norm_bwd_(dqkv, qkv, rstd, wq, wk, H, Hkv, tq, tk, fq and fk)
+    _notify(wq)
+    _notify(wk)
+    return None, None
+
+
+def _attn_packed_bwd(do, qkv, qk, o, lse, cfg, cos, sin, delta=None, qkn=None, rstd=None):
     """Backward attention -> packed dqkv (for the unrotated qkv: the kernels rotate dq / dk back).
-    ``do``: [B, T, H, D] contiguous; ``delta``: rowsum(dO * O) when the caller already holds it."""
+    ``do``: [B, T, H, D] contiguous; ``delta``: rowsum(dO * O) when the caller already holds it.
+    Returns (dqkv, dwq, dwk): with ``qkn`` = (wq, wk, eps) one streaming post-pass takes the q / k
+    columns back through the QK-norm and yields the gain gradients (see _qk_norm_bwd), else None."""
     H, Hkv, D, causal, scale = cfg
     q, k, v = _qkv_heads(qkv, qk, H, Hkv, D)
     dqkv = torch.empty_like(qkv)
     dq, dk, dv = _split_qkv(dqkv, H, Hkv, D)
     _attn_ws(qkv.device)
     _ops().attn_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, cos, sin, delta)
-    return dqkv
+    dwq = dwk = None
+    if qkn is not None:
+        dwq, dwk = _qk_norm_bwd(dqkv, qkv, rstd, qkn[0], qkn[1], H, Hkv)
+    return dqkv, dwq, dwk
 
 
 class _FlashAttnPacked(torch.autograd.Function):
@@ -699,18 +727,21 @@ class _FlashAttnPacked(torch.autograd.Function):
     backward at the llama shape -- the round-2 RoPE A/B record under profiles/ -- and was removed.)"""
 
     @staticmethod
-    def forward(ctx, qkv, H, Hkv, causal, scale, cos, sin):
+    def forward(ctx, qkv, H, Hkv, causal, scale, cos, sin, wq=None, wk=None, qk_eps=1e-5):
         B, T, W = qkv.shape
-        qk, o, lse = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin)
-        ctx.save_for_backward(qkv, qk, o, lse, cos, sin)
+        ctx.qkn = (wq, wk, qk_eps) if wq is not None else None  # QK-norm gains (the parameters themselves)
+        qk, o, lse, rstd = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, ctx.qkn)
+        ctx.save_for_backward(qkv, qk, o, lse, cos, sin, rstd)
         ctx.cfg = (H, Hkv, W // (H + 2 * Hkv), causal, scale)
         return o.view(B, T, -1)
 
     @staticmethod
     def backward(ctx, do):
-        qkv, qk, o, lse, cos, sin = ctx.saved_tensors
-        dqkv = _attn_packed_bwd(do.contiguous().view(o.shape), qkv, qk, o, lse, ctx.cfg, cos, sin)
-        return dqkv, None, None, None, None, None, None
+        qkv, qk, o, lse, cos, sin, rstd = ctx.saved_tensors
+        dqkv, dwq, dwk = _attn_packed_bwd(do.contiguous().view(o.shape), qkv, qk, o, lse, ctx.cfg, cos, sin,
+                                          qkn=ctx.qkn, rstd=rstd)
+        ctx.qkn = None
+        return dqkv, None, None, None, None, None, None, dwq, dwk, None
 
 
 class _AttnProjFn(torch.autograd.Function):
@@ -721,11 +752,12 @@ class _AttnProjFn(torch.autograd.Function):
     dim 64 (a wave's 64 output columns are one head).  Same math as _FlashAttnPacked + _LinearFn."""
 
     @staticmethod
-    def forward(ctx, qkv, H, Hkv, causal, scale, cos, sin, w, b, bias_ext, res=None):
+    def forward(ctx, qkv, H, Hkv, causal, scale, cos, sin, w, b, bias_ext, res=None, wq=None, wk=None, qk_eps=1e-5):
         B, T, W = qkv.shape
         D = W // (H + 2 * Hkv)
-        qk, o, lse = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin)
-        ctx.save_for_backward(qkv, qk, o, lse, cos, sin)
+        ctx.qkn = (wq, wk, qk_eps) if wq is not None else None  # QK-norm gains (the parameters themselves)
+        qk, o, lse, rstd = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, ctx.qkn)
+        ctx.save_for_backward(qkv, qk, o, lse, cos, sin, rstd)
         ctx.cfg = (H, Hkv, D, causal, scale)
         ctx.w, ctx.b, ctx.bias_ext = w, b, bias_ext
         ctx.has_res = res is not None
@@ -737,10 +769,10 @@ class _AttnProjFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        qkv, qk, o, lse, cos, sin = ctx.saved_tensors
+        qkv, qk, o, lse, cos, sin, rstd = ctx.saved_tensors
         H, Hkv, D, causal, scale = ctx.cfg
-        w, b = ctx.w, ctx.b
-        ctx.w = ctx.b = None
+        w, b, qkn = ctx.w, ctx.b, ctx.qkn
+        ctx.w = ctx.b = ctx.qkn = None
         B, T, _ = qkv.shape
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
         o2 = o.view(B * T, H * D)
@@ -768,8 +800,10 @@ class _AttnProjFn(torch.autograd.Function):
         if wt is None or getattr(w, "_pllm_wT_ver", None) != w._version:
             wt = w.t().contiguous()
         do2, delta = _ops().gemm_tn(dy2, wt, None, 6, o2, None, T)
-        dqkv = _attn_packed_bwd(do2.view(B, T, H, D), qkv, qk, o, lse, ctx.cfg, cos, sin, delta)
-        return dqkv, None, None, None, None, None, None, dw, db, None, (dy if ctx.has_res else None)
+        dqkv, dwq, dwk = _attn_packed_bwd(do2.view(B, T, H, D), qkv, qk, o, lse, ctx.cfg, cos, sin, delta,
+                                          qkn=qkn, rstd=rstd)
+        return (dqkv, None, None, None, None, None, None, dw, db, None, (dy if ctx.has_res else None), dwq, dwk,
+                None)
 
 
 # PLLM_AB attn_proj_fused=0: the output projection's backward on hipBLASLt + the attention's delta pre-pass
@@ -792,13 +826,17 @@ def attn_proj_ok(qkv, n_head: int, n_kv_head: int, w, b) -> bool:
 
 
 def attention_proj(qkv, n_head: int, n_kv_head: int, w, b, causal: bool = True, scale: Optional[float] = None,
-                   rope_cos=None, rope_sin=None, bias_grad_external: bool = False, residual=None):
+                   rope_cos=None, rope_sin=None, bias_grad_external: bool = False, residual=None,
+                   q_norm_weight=None, k_norm_weight=None, qk_norm_eps: float = 1e-5):
     """``linear(attention_packed(qkv, ...), w, b)`` (+ ``residual``, added by the GEMM) with the fused
     backward (see _AttnProjFn)."""
     D = qkv.shape[-1] // (n_head + 2 * n_kv_head)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     ext = bool(bias_grad_external and b is not None and not (_TORCH_OPS & {"norm", "act"}))
-    return _AttnProjFn.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin, w, b, ext, residual)
+    if q_norm_weight is None:
+        return _AttnProjFn.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin, w, b, ext, residual)
+    return _AttnProjFn.apply(qkv.contiguous(), n_head, n_kv_head, causal, scale, rope_cos, rope_sin, w, b, ext,
+                             residual, q_norm_weight, k_norm_weight, qk_norm_eps)
 
 
 _ATTN_WS_MB = [None]
@@ -849,19 +887,74 @@ def rope_packed(qkv, cos, sin, n_head: int, n_kv_head: int):
     return torch.cat([q.reshape(B, T, -1), k.reshape(B, T, -1), v.reshape(B, T, -1)], -1)
 
 
+class _QKNormPackedFn(torch.autograd.Function):
+    """QK-norm (+ RoPE) of the q and k heads of a packed qkv tensor -> [B, T, (H + Hkv) D]: the attention
+    pre-pass on its own (csrc/qk_norm.hip), for decode and direct use."""
+
+    @staticmethod
+    def forward(ctx, qkv, wq, wk, eps, H, Hkv, cos, sin, pos_offset):
+        qk, rstd = _ops().qk_norm_rope(qkv, wq, wk, eps, H, Hkv, cos, sin, qkv.shape[1], pos_offset)
+        ctx.save_for_backward(qkv, rstd, cos, sin)
+        ctx.wq, ctx.wk = wq, wk
+        ctx.cfg = (H, Hkv, pos_offset)
+        return qk
+
+    @staticmethod
+    def backward(ctx, dqk):
+        qkv, rstd, cos, sin = ctx.saved_tensors
+        H, Hkv, pos_offset = ctx.cfg
+        wq, wk = ctx.wq, ctx.wk
+        ctx.wq = ctx.wk = None
+        d = dqk.contiguous()
+        if cos is not None:  # back through the rotation
+            d = _ops().rope(d, cos, sin, H + Hkv, H + Hkv, qkv.shape[1], pos_offset, True)
+        dqkv = torch.zeros_like(qkv)  # v takes no part
+        dqkv[..., : d.shape[-1]] = d
+        dwq, dwk = _qk_norm_bwd(dqkv, qkv, rstd, wq, wk, H, Hkv)
+        return dqkv, dwq, dwk, None, None, None, None, None, None
+
+
+def qk_norm_packed(qkv, wq, wk, eps: float, n_head: int, n_kv_head: int, cos=None, sin=None, pos_offset: int = 0):
+    """QK-norm of a packed qkv tensor [B, T, (H + 2 Hkv) D]: (q [B,T,H,D], k [B,T,Hkv,D]), each head RMS-normalised
+    over D with the gains ``wq`` / ``wk`` [D] and then rotated when ``cos`` / ``sin`` are given (row t at position
+    t + pos_offset).  Differentiable; the HIP kernels on the GPU, ``reference.qk_norm`` elsewhere."""
+    B, T, W = qkv.shape
+    H, Hkv = n_head, n_kv_head
+    D = W // (H + 2 * Hkv)
+    if _hip_op("attn", qkv):
+        qk = _QKNormPackedFn.apply(qkv.contiguous(), wq, wk, eps, H, Hkv, cos, sin, pos_offset)
+        return qk[..., : H * D].view(B, T, H, D), qk[..., H * D:].view(B, T, Hkv, D)
+    q, k, _ = _split_qkv(qkv, H, Hkv, D)
+    q, k = ref.qk_norm(q, wq, eps), ref.qk_norm(k, wk, eps)
+    if cos is not None:
+        c, s = cos[pos_offset:pos_offset + T], sin[pos_offset:pos_offset + T]
+        q, k = ref.rope(q, c, s), ref.rope(k, c, s)
+    return q, k
+
+
 def attention_packed(qkv, n_head: int, n_kv_head: int, causal: bool = True, scale: Optional[float] = None,
-                     rope_cos: Optional[torch.Tensor] = None, rope_sin: Optional[torch.Tensor] = None):
+                     rope_cos: Optional[torch.Tensor] = None, rope_sin: Optional[torch.Tensor] = None,
+                     q_norm_weight=None, k_norm_weight=None, qk_norm_eps: float = 1e-5):
     """Causal self-attention over a packed qkv tensor. RoPE (if cos/sin given) is
-    applied to the q and k heads first (rotate-half convention)."""
+    applied to the q and k heads first (rotate-half convention); with ``q_norm_weight`` /
+    ``k_norm_weight`` (QK-norm) every q and k head is RMS-normalised over D before that."""
     B, T, W = qkv.shape
     D = W // (n_head + 2 * n_kv_head)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     if _hip_op("attn", qkv):
         # RoPE: one rope_qk pre-pass rotates q / k, the backward kernels rotate dq / dk back
-        return _FlashAttnPacked.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin)
-    if rope_cos is not None:
-        qkv = rope_packed(qkv, rope_cos, rope_sin, n_head, n_kv_head)
-    q, k, v = _split_qkv(qkv, n_head, n_kv_head, D)
+        if q_norm_weight is None:
+            return _FlashAttnPacked.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin)
+        # QK-norm: qk_norm_rope is that pre-pass, qk_norm_bwd_ a post-pass over dqkv
+        return _FlashAttnPacked.apply(qkv.contiguous(), n_head, n_kv_head, causal, scale, rope_cos, rope_sin,
+                                      q_norm_weight, k_norm_weight, qk_norm_eps)
+    if q_norm_weight is not None:
+        q, k = qk_norm_packed(qkv, q_norm_weight, k_norm_weight, qk_norm_eps, n_head, n_kv_head, rope_cos, rope_sin)
+        v = _split_qkv(qkv, n_head, n_kv_head, D)[2]
+    else:
+        if rope_cos is not None:
+            qkv = rope_packed(qkv, rope_cos, rope_sin, n_head, n_kv_head)
+        q, k, v = _split_qkv(qkv, n_head, n_kv_head, D)
     if _stock("attn") and qkv.is_cuda:
         # stock-PyTorch baseline path (SDPA), used only by the explicit torch backend
         qh, kh, vh = (t.transpose(1, 2) for t in (q, k, v))

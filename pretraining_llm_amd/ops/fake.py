@@ -104,6 +104,20 @@ def register() -> None:
     def _(x, cos, sin, n_heads_total, n_rot, T):
         return x.new_empty((*x.shape[:-1], x.shape[-1] // n_heads_total * n_rot))
 
+    @_reg("qk_norm_rope")
+    def _(qkv, wq, wk, eps, n_head, n_kv_head, cos, sin, T, pos_offset=0):
+        W = qkv.shape[-1]
+        D = W // (n_head + 2 * n_kv_head)
+        rows = qkv.numel() // W
+        return (qkv.new_empty((*qkv.shape[:-1], (n_head + n_kv_head) * D)),
+                qkv.new_empty((rows, n_head + n_kv_head), dtype=f32))
+
+    @_reg("qk_norm_bwd_")
+    def _(dqkv, qkv, rstd, wq, wk, n_head, n_kv_head, dwq_acc, dwk_acc, overwrite):
+        if dwq_acc is not None:
+            return wq.new_empty((0,)), wk.new_empty((0,))
+        return wq.new_empty((wq.numel(),)), wk.new_empty((wk.numel(),))
+
     @_reg("scale_")
     def _(x, s):
         return None

@@ -39,6 +39,11 @@ def rms_norm(x, weight, eps: float):
     return y.to(x.dtype)
 
 
+def qk_norm(x, weight, eps: float):
+    """QK-norm: RMSNorm over the head dimension of x [B,T,H,D] with one gain vector ``weight`` [D]."""
+    return rms_norm(x, weight, eps)
+
+
 def attention(q, k, v, causal: bool = True, scale: Optional[float] = None):
     """q: [B,T,H,D], k/v: [B,S,Hkv,D] -> out [B,T,H,D], lse [B,H,T] (natural log)."""
     B, T, H, D = q.shape

@@ -43,13 +43,23 @@ from .optim import FlatAdamW, no_decay_1d
 def model_config_from(cfg: dict) -> ModelConfig:
     preset = cfg.get("model_preset")
     dims = {k: cfg[k] for k in ("vocab_size", "context_length", "n_embed", "n_head", "n_blocks") if k in cfg}
-    extra = {k: cfg[k] for k in ("n_kv_head", "ffn_hidden", "activation_checkpointing") if cfg.get(k) is not None}
+    extra = {k: cfg[k] for k in ("n_kv_head", "ffn_hidden", "activation_checkpointing", "qk_norm", "qk_norm_eps")
+             if cfg.get(k) is not None}
     if preset:
         mc = get_preset(preset)
         over = {k: v for k, v in {**dims, **extra}.items() if cfg.get("override_preset_dims", False) or k in extra}
         return mc.replace(**over) if over else mc
     from ..models.config import _ref
     return _ref(**dims, **extra)
+
+
+def check_parallel_config(cfg: dict) -> None:
+    """Combinations the model-parallel layouts do not cover, rejected before any process group exists."""
+    tp, cp = int(cfg.get("tp_size", 1)), int(cfg.get("cp_size", 1))
+    if (tp > 1 or cp > 1) and model_config_from(cfg).qk_norm:
+        raise ValueError(f"qk_norm is not supported with tensor or context parallelism (tp_size={tp}, "
+                         f"cp_size={cp}): under TP the replicated gains see only the local heads and their "
+                         "gradients would need a TP-group sum; ring / Ulysses attention take their own path")
 
 
 def lr_at(step: int, cfg: dict) -> float:
@@ -74,6 +84,7 @@ class Trainer:
     def __init__(self, cfg: dict, dist_info: Optional[DistInfo] = None, log=print):
         self.cfg = dict(cfg)
         self.log = log
+        check_parallel_config(self.cfg)
         if dist_info is None:  # RCCL's environment must be in place before the communicator exists
             apply_rccl_env(self.cfg.get("rccl_channels"), parse_env_list(self.cfg.get("rccl_env")))
         self.di = dist_info or init_distributed(self.cfg.get("ddp_backend", "auto"), self.cfg.get("device", "auto"))
