@@ -94,6 +94,8 @@ default_config = {
     'activation_checkpointing': None,
     'qk_norm': None,                  # True: RMSNorm over head_dim of every q / k head before RoPE (None -> the preset's)
     'qk_norm_eps': None,
+    'doc_mask': None,                 # True: a token attends only to its own document of the packed window (None -> the preset's)
+    'doc_sep_token': None,            # the token that ends a document (None -> the preset's: 50256, the data pipeline's end-of-text)
     'override_preset_dims': False,    # with model_preset: the dims above (n_embed, n_head, n_blocks, ...) override the preset's
     'tuned_gemms': True,              # GPU: load the shipped TunableOp GEMM selections (pretraining_llm_amd/tuning/)
     'tp_size': 1,                     # tensor parallelism: heads / FFN columns sharded (parallel/model_parallel.py)

@@ -77,7 +77,13 @@ struct FwdCfg {
   static constexpr int LDS_ELEMS = 4 * TILE;
 };
 
-template <int D>
+// SEG: per-row key bounds (a.kv_start: document / window masks; causal, S == T) -- query i sees keys
+// kv_start[b, i] <= j <= i.  kv_start is non-decreasing, so a block's smallest bound is its first row's
+// and its largest its last row's: the tile loop starts at the workgroup's first visible tile, a wave's
+// block skips tiles that end before its first row's bound, and tiles that begin before its last row's
+// bound take the per-element compare (against a second per-lane limit).  Rows whose first processed
+// tiles are wholly masked run with m = -inf through the guards of the lazy-max update below.
+template <int D, bool SEG>
 __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_kernel(AttnFwdArgs a) {
   using C = FwdCfg<D>;
   using I = Img<D>;
@@ -107,6 +113,22 @@ __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_
   for (int j = 0; j < QB; ++j) {
     qw[j] = q0 + 32 * (j == 0 ? w : 2 * NW - 1 - w);
     qend[j] = qw[j] >= a.T ? 0 : (a.causal ? min(a.S, qw[j] + 32 + off) : a.S);
+  }
+  // SEG: the lane's lower key bound, and the bounds of each block's first / last row (wave-uniform)
+  int klo[QB], klo_first[QB], klo_last[QB];
+  int t0 = 0;
+  if constexpr (SEG) {
+    const int* ksp = a.kv_start + (int64_t)b * a.T;
+#pragma unroll
+    for (int j = 0; j < QB; ++j) {
+      klo[j] = ksp[min(qw[j] + r, a.T - 1)];
+      if (hh == 0 && qw[j] + r < a.T) PL_DCHECK(klo[j] >= 0 && klo[j] <= qw[j] + r, "0 <= kv_start[i] <= i", klo[j]);
+      klo_first[j] = __builtin_amdgcn_readfirstlane(ksp[min(qw[j], a.T - 1)]);
+      klo_last[j] = __builtin_amdgcn_readfirstlane(ksp[min(qw[j] + 31, a.T - 1)]);
+    }
+    // the workgroup's first visible tile (q0 < T); clamped so that a bound outside the contract
+    // 0 <= kv_start[i] <= i cannot move the tile DMA out of the key rows
+    t0 = min(max(ksp[q0], 0), q0) / BN;
   }
   bf16x8 qf[QB][NKS];
 #pragma unroll
@@ -177,12 +199,12 @@ __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_
   uint64_t st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const uint64_t st_start = __builtin_amdgcn_s_memtime();
 #endif
-  if (ntiles > 0) {
-    gdma(0, 0);
+  if (ntiles > t0) {
+    gdma(t0, t0 & 1);
     vm_wait_all();
   }
   __syncthreads();
-  for (int t = 0; t < ntiles; ++t) {
+  for (int t = t0; t < ntiles; ++t) {
 #if PLLM_FWD_STAMPS
     uint64_t ts_prev = __builtin_amdgcn_s_memtime();
     auto stamp = [&](int i) {
@@ -200,7 +222,9 @@ __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_
     const int kv0 = t * BN;
     // which of this wave's blocks see keys of this tile: a compile-time mask per code
     // path, so no MFMA is predicated (an if-converted MFMA keeps both results live)
-    const int mask = (kv0 < qend[0] ? 1 : 0) | (QB > 1 && kv0 < qend[QB - 1] ? 2 : 0);
+    int mask = (kv0 < qend[0] ? 1 : 0) | (QB > 1 && kv0 < qend[QB - 1] ? 2 : 0);
+    if constexpr (SEG)  // ... and that do not end before the block's first row's bound
+      mask &= (kv0 + BN > klo_first[0] ? 1 : 0) | (QB > 1 && kv0 + BN > klo_first[QB - 1] ? 2 : 0);
     auto tile = [&](auto mask_c) {
       constexpr int MASK = decltype(mask_c)::value;
       const uint16_t* Kb = smem + buf * TILE;
@@ -235,7 +259,8 @@ __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_
       for (int j = 0; j < QB; ++j) {
         if (!((MASK >> j) & 1)) continue;
         const int qi = qw[j] + r;
-        const bool need_mask = (kv0 + BN > a.S) || (a.causal && kv0 + BN - 1 > qw[j] + off);
+        bool need_mask = (kv0 + BN > a.S) || (a.causal && kv0 + BN - 1 > qw[j] + off);
+        if constexpr (SEG) need_mask = need_mask || kv0 < klo_last[j];
         if (need_mask) {
           // element i of key half kb is key kv0 + 32 kb + 4 hh + acc_row(i, 0): dead past S or
           // after the lane's query -- one compare per element against a per-lane limit (a
@@ -245,7 +270,12 @@ __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_
           for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
             for (int i = 0; i < 16; ++i)
-              s[j][kb][i] = acc_row(i, 0) > lim0 - 32 * kb ? -INFINITY : s[j][kb][i];
+              if constexpr (SEG) {  // ... or before the lane's query's bound
+                const int lo0 = klo[j] - (kv0 + 4 * hh);
+                s[j][kb][i] = acc_row(i, 0) < lo0 - 32 * kb || acc_row(i, 0) > lim0 - 32 * kb ? -INFINITY : s[j][kb][i];
+              } else {
+                s[j][kb][i] = acc_row(i, 0) > lim0 - 32 * kb ? -INFINITY : s[j][kb][i];
+              }
           }
         }
         // two independent max / sum chains per lane (ILP), then the lane pair (r, r+32)
@@ -411,7 +441,12 @@ struct BwdCfg {
 // on the whole backward: the slab bytes are its second cost after the MFMAs.
 // ROT_BACK (RoPE): q and k arrive rotated (the caller's rope_qk pre-pass); dk is rotated back before
 // its store here and dq in the reduce, so the gradients are those of the unrotated tensors.
-template <int D, bool ROT_BACK>
+// SEG (per-row key bounds, a.q_last: causal, S == T): key j is seen by queries j <= i <= q_last[b, j], one
+// more per-lane limit in the MASKED body.  q_last is non-decreasing, so the sweep over the query blocks ends
+// with the block of the key block's last key's q_last (no slab rows are written past it: the reduce starts
+// at kmin), and a wave's sub-block needs the masked path when it reaches past its first key's q_last.
+// Sub-blocks inside the sweep that no key of the wave sees are masked to zero, not skipped.
+template <int D, bool ROT_BACK, bool SEG>
 __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_bwd_kernel(AttnBwdArgs a) {
   using C = BwdCfg<D>;
   using I = Img<D>;
@@ -485,7 +520,16 @@ __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_
     }
   const float c2 = a.scale_log2;
   const int g1 = (lane >> 4) & 1, i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;
-  const int nqb = (a.T + BQ - 1) / BQ;
+  int nqb = (a.T + BQ - 1) / BQ;
+  // SEG: the lane's keys' last queries, the wave's first key's (its smallest), and the end of the sweep
+  int qhi[KH], qhi_w = 0;
+  if constexpr (SEG) {
+    const int* qlp = a.q_last + (int64_t)b * a.S;
+#pragma unroll
+    for (int kh = 0; kh < KH; ++kh) qhi[kh] = qlp[min(kw0 + 32 * kh + r, a.S - 1)];
+    qhi_w = __builtin_amdgcn_readfirstlane(qlp[min(kw0, a.S - 1)]);
+    nqb = min(nqb, qlp[min(k0 + BK, a.S) - 1] / BQ + 1);
+  }
   int qb_start = 0;
   if (a.causal) qb_start = max(0, k0 - off) / BQ;
   const int per_head = nqb - qb_start;
@@ -743,12 +787,13 @@ __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_
         // key > query; keys past S: all).  Query rows past T need no test: their Q / dO rows
         // are zero-filled and their row constants 0, so P = 1 meets dO = 0 (dV) and dS = 0
         // (dK, dQ), and no dQ row past T is stored.
-        int lo[NL];
+        int lo[NL], hi[NL];
         if constexpr (MASKED) {
 #pragma unroll
           for (int kh = 0; kh < NL; ++kh) {
             const int key = kw0 + 32 * kh + r;
             lo[kh] = key >= a.S ? 64 : (a.causal ? key - off - (qj0 + 4 * hh) : -64);
+            if constexpr (SEG) hi[kh] = qhi[kh] - (qj0 + 4 * hh);  // ... or acc_row(i) > hi[kh]: past q_last[key]
           }
         }
         bf16x8 pf[NL][2], sf[NL][2];
@@ -762,7 +807,8 @@ __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_
             for (int e = 0; e < 4; ++e) {
               const int i = 4 * g + e;
               float p = fast_exp2(__builtin_fmaf(s[kh][i], c2, rs[e]));
-              if constexpr (MASKED) p = acc_row(i, 0) < lo[kh] ? 0.f : p;
+              if constexpr (MASKED && SEG) p = acc_row(i, 0) < lo[kh] || acc_row(i, 0) > hi[kh] ? 0.f : p;
+              else if constexpr (MASKED) p = acc_row(i, 0) < lo[kh] ? 0.f : p;
               s[kh][i] = p;               // P
               dp[kh][i] = p * dp[kh][i];  // dS (unscaled; dP accumulated onto -delta)
             }
@@ -822,7 +868,8 @@ __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_
       using FF = std::false_type;
       // per wave and sub-block: only the sub-block whose 32 queries overlap the wave's keys
       // (the causal diagonal) or a ragged key end needs the masked path
-      const bool mask_j = need_mask && ((kw0 + 32 * KH > a.S) || (a.causal && kw0 + 32 * KH - 1 > qj0 + off));
+      bool mask_j = need_mask && ((kw0 + 32 * KH > a.S) || (a.causal && kw0 + 32 * KH - 1 > qj0 + off));
+      if constexpr (SEG) mask_j = mask_j || qhi_w < qj0 + 31;
       if (live == KH) {
         if (mask_j) body(std::integral_constant<int, KH>{}, TT{});
         else body(std::integral_constant<int, KH>{}, FF{});
@@ -943,7 +990,11 @@ __global__ __launch_bounds__((BwdCfg<D>::NT), (BwdCfg<D>::MIN_WAVES)) void attn_
 // (deterministic) into the fp32 running sum (kept in the same fragment order) or, on the last
 // pass, transposes the tile through LDS and writes dq = scale * total as whole 16-B row chunks,
 // rotated back (ROT_BACK: RoPE, each thread holds a dim chunk and its d + D/2 partner).
-template <int D, bool ROT_BACK>
+// SEG (per-row key bounds): a key block's sweep ends with the block of its last key's q_last, so it wrote
+// this tile's rows iff it is not wholly before the tile's first query's kv_start (kv_start and q_last are
+// non-decreasing): the sum starts at key block kmin = kv_start[b, 32 qt] / BK, clamped to the pass.  A pass
+// that lies wholly before kmin adds nothing and hands the running sum on.
+template <int D, bool ROT_BACK, bool SEG>
 __global__ __launch_bounds__(256) void attn_dq_reduce_frag_kernel(AttnBwdArgs a) {
   constexpr int BK = pllm::kAttnBwdKeyBlock;
   constexpr int NDB = D / 32, NTH = 64 * NDB, LD = D + 4;  // LD: padded fp32 row of the LDS tile
@@ -969,6 +1020,7 @@ __global__ __launch_bounds__(256) void attn_dq_reduce_frag_kernel(AttnBwdArgs a)
   // four slabs' loads in flight before their adds (the adds keep key-block order: deterministic); one
   // slab per trip left each thread one memory round trip per key block (2.9 TB/s at the llama shape)
   int kb = a.kb0;
+  if constexpr (SEG) kb = max(kb, a.kv_start[(int64_t)b * a.T + qt * 32] / BK);  // qt * 32 < T
   for (; kb + 3 <= kmax; kb += 4) {
     u32x4 v[4][2];
 #pragma unroll
@@ -1047,7 +1099,9 @@ bool attn_supported_head_dim(int D) { return D == 32 || D == 64 || D == 128; }
 template <int D>
 static void attn_fwd_t(const AttnFwdArgs& a, hipStream_t st) {
   const int nqb = (a.T + FwdCfg<D>::BM - 1) / FwdCfg<D>::BM;
-  hipLaunchKernelGGL(attn_fwd_kernel<D>, dim3(nqb * a.B * a.H), dim3(64 * FwdCfg<D>::NW), 0, st, a);
+  const dim3 grid(nqb * a.B * a.H), blk(64 * FwdCfg<D>::NW);
+  if (a.kv_start) hipLaunchKernelGGL((attn_fwd_kernel<D, true>), grid, blk, 0, st, a);
+  else hipLaunchKernelGGL((attn_fwd_kernel<D, false>), grid, blk, 0, st, a);
 }
 
 void attn_fwd(const AttnFwdArgs& a, hipStream_t st) {
@@ -1069,7 +1123,9 @@ static void attn_bwd_passes(AttnBwdArgs a, hipStream_t st, LaunchMain launch_mai
   const int pre_grid = (int)((nrows * (D / 8) + 255) / 256);
   const int nkb = (a.S + BK - 1) / BK;
   const int red_grid = a.B * a.H * a.nqt;  // one workgroup per 32-query tile
-  const BwdKernel reduce = a.rope_cos ? attn_dq_reduce_frag_kernel<D, true> : attn_dq_reduce_frag_kernel<D, false>;
+  const BwdKernel reduce =
+      a.q_last ? (a.rope_cos ? attn_dq_reduce_frag_kernel<D, true, true> : attn_dq_reduce_frag_kernel<D, false, true>)
+               : (a.rope_cos ? attn_dq_reduce_frag_kernel<D, true, false> : attn_dq_reduce_frag_kernel<D, false, false>);
   if (!a.delta_ready) hipLaunchKernelGGL(attn_bwd_pre_kernel<D>, dim3(pre_grid), dim3(256), 0, st, a);
   const int per = a.nkb_pass;
   for (int kb0 = 0; kb0 < nkb; kb0 += per) {
@@ -1085,7 +1141,8 @@ static void attn_bwd_passes(AttnBwdArgs a, hipStream_t st, LaunchMain launch_mai
 template <int D>
 static void attn_bwd_fused_launch(const AttnBwdArgs& a, hipStream_t st) {
   static_assert(BwdCfg<D>::BK == kAttnBwdKeyBlock, "one key-block size for every backward kernel");
-  const BwdKernel main = a.rope_cos ? attn_bwd_kernel<D, true> : attn_bwd_kernel<D, false>;
+  const BwdKernel main = a.q_last ? (a.rope_cos ? attn_bwd_kernel<D, true, true> : attn_bwd_kernel<D, false, true>)
+                                  : (a.rope_cos ? attn_bwd_kernel<D, true, false> : attn_bwd_kernel<D, false, false>);
   hipLaunchKernelGGL(main, dim3(a.nkb_pass * a.B * a.Hkv), dim3(BwdCfg<D>::NT), 0, st, a);
 }
 

@@ -75,7 +75,10 @@ struct ImgT {
 };
 
 // ROT_BACK (RoPE): q / k arrive rotated, dk is rotated back before its store (dq in the reduce)
-template <int D, bool ROT_BACK>
+// SEG (per-row key bounds, a.q_last: causal, S == T): key j is seen by queries j <= i <= q_last[b, j] -- a
+// second per-lane limit in the S accumulators' initialisers, and the sweep ends with the slice of the key
+// block's last key's q_last (q_last is non-decreasing; the reduce starts at the matching kmin)
+template <int D, bool ROT_BACK, bool SEG>
 __global__ __launch_bounds__(256, 1) void attn_bwd_ks_kernel(AttnBwdArgs a) {
   using C = KsCfg<D>;
   using I = Img<D>;
@@ -108,7 +111,16 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_ks_kernel(AttnBwdArgs a) {
   const uint16_t* vp = a.v + b * a.v_sb + (int64_t)hk * a.v_sh;
 
   // ---- sweep bounds: (query head of the group, BQ-query slice), causal slices from the key block on
-  const int nqs = (a.T + BQ - 1) / BQ;
+  int nqs = (a.T + BQ - 1) / BQ;
+  // SEG: the lane's two keys' last queries, the wave's first key's (its smallest), and the end of the sweep
+  int qhi[2], qhi_w = 0;
+  if constexpr (SEG) {
+    const int* qlp = a.q_last + (int64_t)b * a.S;
+#pragma unroll
+    for (int kh = 0; kh < 2; ++kh) qhi[kh] = qlp[min(kw0 + 32 * kh + r, a.S - 1)];
+    qhi_w = __builtin_amdgcn_readfirstlane(qlp[min(kw0, a.S - 1)]);
+    nqs = min(nqs, qlp[min(k0 + BK, a.S) - 1] / BQ + 1);
+  }
   const int qs_start = a.causal ? max(0, k0 - off) / BQ : 0;
   const int per_head = max(0, nqs - qs_start);
   const int total = per_head * G;
@@ -259,7 +271,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_ks_kernel(AttnBwdArgs a) {
       // branch before the straight-line steps; a sub-block whose keys all follow its queries is fully
       // masked rather than skipped (one wave per SIMD: a skip saves no wall time, and a branch around
       // the dK / dV updates made hipcc copy the 256 accumulators at the join).
-      const bool mask_j = !aligned || (a.causal && kw0 + 63 > qj0 + off);  // wave-uniform
+      bool mask_j = !aligned || (a.causal && kw0 + 63 > qj0 + off);  // wave-uniform
+      if constexpr (SEG) mask_j = mask_j || qhi_w < qj0 + 31;
       f32x16 s0, s1, d0, d1;
       if (mask_j) {
 #pragma unroll
@@ -268,7 +281,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_ks_kernel(AttnBwdArgs a) {
           const int lo = key >= a.S ? 64 : (a.causal ? key - off - (qj0 + 4 * hh) : -64);
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
-            const float mv = acc_row(i, 0) < lo ? -INFINITY : 0.f;
+            float mv = acc_row(i, 0) < lo ? -INFINITY : 0.f;
+            if constexpr (SEG) mv = acc_row(i, 0) > qhi[kh] - (qj0 + 4 * hh) ? -INFINITY : mv;  // past q_last[key]
             if (kh == 0) s0[i] = mv;
             else s1[i] = mv;
           }
@@ -517,8 +531,14 @@ namespace pllm {
 // slab reduce after)
 void attn_bwd_ks_launch(const AttnBwdArgs& a, hipStream_t st) {
   const dim3 grid(a.nkb_pass * a.B * a.Hkv), blk(256);
-  if (a.rope_cos) hipLaunchKernelGGL((attn_bwd_ks_kernel<128, true>), grid, blk, 0, st, a);
-  else hipLaunchKernelGGL((attn_bwd_ks_kernel<128, false>), grid, blk, 0, st, a);
+  if (a.q_last) {
+    if (a.rope_cos) hipLaunchKernelGGL((attn_bwd_ks_kernel<128, true, true>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((attn_bwd_ks_kernel<128, false, true>), grid, blk, 0, st, a);
+  } else if (a.rope_cos) {
+    hipLaunchKernelGGL((attn_bwd_ks_kernel<128, true, false>), grid, blk, 0, st, a);
+  } else {
+    hipLaunchKernelGGL((attn_bwd_ks_kernel<128, false, false>), grid, blk, 0, st, a);
+  }
 }
 
 }  // namespace pllm

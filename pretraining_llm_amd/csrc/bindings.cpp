@@ -960,7 +960,25 @@ void check_rope(const std::optional<Tensor>& c, const std::optional<Tensor>& sn,
   }
 }
 
-std::vector<Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, bool causal, double scale) {
+// Optional per-row key bounds of attn_fwd / attn_bwd (document and window masks): query i of batch row b
+// sees keys kv_start[b, i] <= j <= i, equivalently j <= i <= q_last[b, j].  Contract (not validated on the
+// device): kv_start is non-decreasing along T with 0 <= kv_start[b, i] <= i, and q_last[b, j] is the last i
+// with kv_start[b, i] <= j (ops.doc_bounds / ops.bounds_from_start build both).  Bounds need causal and S == T.
+static const int* check_bound(const std::optional<Tensor>& t, const Tensor& q, int64_t B, int64_t n, int64_t S,
+                              int64_t T, bool causal, const char* name) {
+  if (!t) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->device() == q.device(), "attention: ", name, " must be on the device of q");
+  TORCH_CHECK(t->scalar_type() == at::kInt, "attention: ", name, " must be int32");
+  TORCH_CHECK(t->dim() == 2 && t->size(0) == B && t->size(1) == n, "attention: ", name, " must have shape [B, ",
+              n, "], got ", t->sizes());
+  TORCH_CHECK(t->is_contiguous(), "attention: ", name, " must be contiguous");
+  TORCH_CHECK(causal, "attention: ", name, " needs causal attention");
+  TORCH_CHECK(S == T, "attention: ", name, " needs S == T, got S = ", S, ", T = ", T);
+  return t->data_ptr<int>();
+}
+
+std::vector<Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, bool causal, double scale,
+                             const std::optional<Tensor>& kv_start) {
   const int64_t D = q.size(3);
   TORCH_CHECK(pllm::attn_supported_head_dim((int)D), "attention: head dim must be 32, 64 or 128, got ", D);
   check_head_view(q, "q", D);
@@ -988,6 +1006,7 @@ std::vector<Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, 
   a.scale = (float)scale;
   a.scale_log2 = (float)(scale * 1.4426950408889634);
   a.causal = causal ? 1 : 0;
+  a.kv_start = check_bound(kv_start, q, B, T, S, T, causal, "kv_start");
   // diagnostic (a PLLM_FWD_STAMPS=1 build of attention.hip + this env): per-wave phase cycles of
   // the forward's tile loop, summed and printed to stderr after the launch
   static const bool stamps = std::getenv("PLLM_FWD_STAMPS") != nullptr;
@@ -1071,7 +1090,8 @@ int64_t attn_bwd_ws_bytes() {
 // back rotated back, i.e. as the gradients of the unrotated heads
 void attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o, const Tensor& lse,
               Tensor& dq, Tensor& dk, Tensor& dv, bool causal, double scale, const std::optional<Tensor>& rope_cos,
-              const std::optional<Tensor>& rope_sin, const std::optional<Tensor>& delta_in) {
+              const std::optional<Tensor>& rope_sin, const std::optional<Tensor>& delta_in,
+              const std::optional<Tensor>& kv_start, const std::optional<Tensor>& q_last) {
   const int64_t D = q.size(3);
   TORCH_CHECK(pllm::attn_supported_head_dim((int)D), "attention: head dim must be 32, 64 or 128");
   for (auto& pr : std::vector<std::pair<const Tensor*, const char*>>{
@@ -1136,6 +1156,9 @@ void attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor
   a.scale_log2 = (float)(scale * 1.4426950408889634);
   a.causal = causal ? 1 : 0;
   a.delta_ready = delta_in ? 1 : 0;
+  TORCH_CHECK(kv_start.has_value() == q_last.has_value(), "attn_bwd: kv_start and q_last go together (both or neither)");
+  a.kv_start = check_bound(kv_start, q, B, T, S, T, causal, "kv_start");
+  a.q_last = check_bound(q_last, q, B, S, S, T, causal, "q_last");
   static const bool bstamps = std::getenv("PLLM_BWD_STAMPS") != nullptr;
   Tensor bst;
   if (bstamps) {  // diagnostic, with a PLLM_BWD_STAMPS=1 build of attention.hip / attn_bwd_ks.hip
@@ -1199,9 +1222,9 @@ TORCH_LIBRARY(pllm, m) {
   m.def("transpose_run(Tensor desc, int total_tiles) -> ()");
   m.def("sample(Tensor logits, float temperature, int seed) -> Tensor");
   m.def("sample_rows(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor min_p, Tensor seed, Tensor step) -> (Tensor tokens, Tensor kept, Tensor min_kept)");
-  m.def("attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale) -> Tensor[]");
+  m.def("attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, Tensor? kv_start=None) -> Tensor[]");
   m.def("attn_decode(Tensor q, Tensor k, Tensor v, float scale, Tensor? seqlen=None) -> Tensor");
-  m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, Tensor? delta=None) -> ()");
+  m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, Tensor? delta=None, Tensor? kv_start=None, Tensor? q_last=None) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(pllm, CUDA, m) {

@@ -15,6 +15,9 @@ struct AttnFwdArgs {
   float scale, scale_log2;
   int causal;
   unsigned long long* stamps;  // diagnostic builds only (PLLM_FWD_STAMPS): per-wave phase cycles
+  // optional per-row key bounds (document / window masks; causal, S == T): query i sees keys
+  // kv_start[b, i] <= j <= i.  int32 [B, T], non-decreasing along T, 0 <= kv_start[i] <= i.  Null: plain causal
+  const int* kv_start;
 };
 
 // q [B, H, D] (one query per sequence), k/v rows of a [B, S_max, Hkv, D]-strided cache
@@ -49,6 +52,9 @@ struct AttnBwdArgs {
   int causal;
   unsigned long long* stamps;  // diagnostic builds only (PLLM_BWD_STAMPS): per-wave phase cycles
   int delta_ready;             // 1: delta already holds rowsum(dO * O) (gemm_tn epilogue 6): no pre-pass
+  // optional per-row key bounds (see AttnFwdArgs; both or neither): q_last[b, j] int32 [B, S] is the last
+  // query that sees key j, so visibility is kv_start[i] <= j <= i  <=>  j <= i <= q_last[j]
+  const int *kv_start, *q_last;
 };
 
 namespace pllm {

@@ -217,7 +217,8 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float =
         if not use_cache:
             for step in range(max_new_tokens):
                 idx_cond = idx[:, -ctx_len:]
-                logits, _ = model(idx_cond)
+                # the context is one document, as it is for the KV-cache path (no document masking)
+                logits, _ = model(idx_cond, doc_mask=False)
                 nxt = sample_next(logits[:, -1, :].float(), temperature, top_k, generator, top_p, min_p, seed, step)
                 idx = torch.cat([idx, nxt], dim=1)
             return idx

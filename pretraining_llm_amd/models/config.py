@@ -44,6 +44,11 @@ class ModelConfig:
     # gain vector of head_dim each per block, after the QKV projection and before RoPE
     qk_norm: bool = False
     qk_norm_eps: float = 1e-5
+    # Document masking (packed pretraining): a token attends only to its own document, the documents of a window
+    # being delimited by doc_sep_token (the data pipeline's end-of-text token, the LAST token of the document it
+    # ends).  No parameters; positions are unchanged; KV-cache generation treats its context as one document
+    doc_mask: bool = False
+    doc_sep_token: int = 50256
     init: str = "gpt2"                      # gpt2 | torch_default
     init_std: float = 0.02
     # True / False, a float fraction of the blocks, or "auto": checkpoint only as many blocks as
@@ -59,6 +64,9 @@ class ModelConfig:
         if self.qk_norm and self.arch == "ref":
             raise ValueError("qk_norm is not available with arch='ref': the reference checkpoint layout "
                              "(per-head key / query / value weights) has no place for the gains")
+        if self.doc_mask and not 0 <= self.doc_sep_token < self.vocab_size:
+            raise ValueError(f"doc_mask: doc_sep_token={self.doc_sep_token} is outside the vocabulary "
+                             f"[0, {self.vocab_size})")
         if self.ffn_hidden is None:
             if self.mlp == "swiglu":
                 h = int(2 * (4 * self.n_embed) / 3)

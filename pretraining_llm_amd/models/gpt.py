@@ -88,12 +88,13 @@ class Attention(nn.Module):
         return dict(q_norm_weight=self.q_norm.weight, k_norm_weight=self.k_norm.weight,
                     qk_norm_eps=self.cfg.qk_norm_eps)
 
-    def forward(self, x, rope=None, fuse_out_bias: bool = False):
-        return self.forward_res(x, rope, fuse_out_bias)[0]
+    def forward(self, x, rope=None, fuse_out_bias: bool = False, bounds=None):
+        return self.forward_res(x, rope, fuse_out_bias, bounds=bounds)[0]
 
-    def forward_res(self, x, rope=None, fuse_out_bias: bool = False, residual=None):
+    def forward_res(self, x, rope=None, fuse_out_bias: bool = False, residual=None, bounds=None):
         """(y + residual, True) when the fused projection adds the block's residual stream in its GEMM
-        (ops.resid_gemm_ok), else (y, False) and the caller's norm adds it."""
+        (ops.resid_gemm_ok), else (y, False) and the caller's norm adds it.  ``bounds``: the window's
+        per-row key bounds (ops.doc_bounds) under document masking."""
         qkv = ops.linear(x, self.qkv.weight, self.qkv.bias)
         cos, sin = rope if rope is not None else (None, None)
         if self.proj is not None and ops.attn_proj_ok(qkv, self.n_head, self.n_kv_head, self.proj.weight,
@@ -102,9 +103,9 @@ class Attention(nn.Module):
             r = residual if ops.resid_gemm_ok(residual, self.proj.weight) else None
             return ops.attention_proj(qkv, self.n_head, self.n_kv_head, self.proj.weight, self.proj.bias,
                                       rope_cos=cos, rope_sin=sin, bias_grad_external=fuse_out_bias,
-                                      residual=r, **self._qk_norm_kw()), r is not None
+                                      residual=r, bounds=bounds, **self._qk_norm_kw()), r is not None
         y = ops.attention_packed(qkv, self.n_head, self.n_kv_head, causal=True, rope_cos=cos, rope_sin=sin,
-                                 **self._qk_norm_kw())
+                                 bounds=bounds, **self._qk_norm_kw())
         if self.proj is not None:
             r = residual if ops.resid_gemm_ok(residual, self.proj.weight) else None
             return ops.linear(y, self.proj.weight, self.proj.bias, bias_grad_external=fuse_out_bias,
@@ -239,8 +240,9 @@ class Block(nn.Module):
         self.ln2 = Norm(cfg)
         self.mlp = MLP(cfg)
 
-    def forward(self, x, residual=None, rope=None, x_bias=None, fuse_mlp_out_bias: bool = False):
+    def forward(self, x, residual=None, rope=None, x_bias=None, fuse_mlp_out_bias: bool = False, bounds=None):
         """(x, residual) -> (mlp_out, residual_after_attn); the caller's next norm adds them.
+        ``bounds``: per-row key bounds of the attention (document masking), else None.
 
         Fused bias gradients (HIP path): ``x_bias`` is the bias of the layer that produced x (the
         previous block's MLP down projection), emitted by ln1's backward; the attention output
@@ -252,7 +254,9 @@ class Block(nn.Module):
         # the output projections may add the residual stream in their GEMMs (ops.resid_gemm_ok; the reference's
         # x + attn(ln1(x)) / x + mlp(ln2(x)), /root/reference/src/models/transformer_block.py:44,46): then the
         # next norm gets the stream itself (residual None) and the block returns (stream, None)
-        if hasattr(self.attn, "forward_res"):
+        if bounds is not None:  # (doc_mask is rejected under tensor / context parallelism: the dense Attention)
+            a, a_res = self.attn.forward_res(h, rope, fuse, res, bounds=bounds)
+        elif hasattr(self.attn, "forward_res"):
             a, a_res = self.attn.forward_res(h, rope, fuse, res)
         else:
             a, a_res = self.attn(h, rope, fuse_out_bias=fuse), False
@@ -465,7 +469,7 @@ class GPT(nn.Module):
                 targets = zigzag_shard(targets, 1, pg.cp_group) if targets is not None else None
         return idx, targets
 
-    def _trunk(self, idx):
+    def _trunk(self, idx, doc_mask: Optional[bool] = None):
         pos = self._cp_positions(idx)
         pg = self.parallel
         if pg is not None and pg.sequence_parallel:
@@ -484,24 +488,32 @@ class GPT(nn.Module):
         rope = self.rope_tables(idx.device, idx.shape[1] if pos is None else self.config.context_length)
         if rope is not None and pos is not None:
             rope = (rope[0].index_select(0, pos).contiguous(), rope[1].index_select(0, pos).contiguous())
+        # document masking: the window's per-row key bounds, once for all blocks (fixed-shape device ops)
+        bounds = None
+        if self.config.doc_mask if doc_mask is None else doc_mask:
+            if pg is not None and pg.model_parallel:
+                raise ValueError("doc_mask is not supported with tensor or context parallelism")
+            bounds = ops.doc_bounds(idx, self.config.doc_sep_token)
         res = None
         n_ckpt = self.checkpointed_blocks(idx) if self.training and torch.is_grad_enabled() else 0
         x_bias = None  # bias of the layer that produced x (fused into the next norm's backward)
         for i, blk in enumerate(self.attn_blocks):
             if i < n_ckpt:
-                x, res = checkpoint(blk, x, res, rope, x_bias, True, use_reentrant=False)
+                x, res = checkpoint(blk, x, res, rope, x_bias, True, bounds, use_reentrant=False)
             else:
-                x, res = blk(x, res, rope, x_bias, True)
+                x, res = blk(x, res, rope, x_bias, True, bounds)
             x_bias = blk.fused_out_bias(x)
         h, _ = self.layer_norm(x, res, x_bias=x_bias)
         return h
 
     def forward(self, idx: torch.Tensor, targets: Optional[torch.Tensor] = None,
-                return_logits: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+                return_logits: bool = True,
+                doc_mask: Optional[bool] = None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
         """Under tensor/sequence/context parallelism the loss is the mean over THIS rank's tokens
-        (SP / CP: its sequence shard); the Trainer scales the gradients accordingly."""
+        (SP / CP: its sequence shard); the Trainer scales the gradients accordingly.
+        ``doc_mask``: None follows ``config.doc_mask``; False runs the window as one document (generation)."""
         idx, targets = self._shard_inputs(idx, targets)
-        h = self._trunk(idx)
+        h = self._trunk(idx, doc_mask)
         pg = self.parallel
         if targets is not None and pg is not None and pg.sequence_parallel:
             from ..parallel.tensor import _split_dim

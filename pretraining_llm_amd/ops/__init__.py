@@ -667,7 +667,41 @@ def _qkv_heads(qkv, qk, H, Hkv, D):
     return q, k, v
 
 
-def _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, qkn=None):
+def doc_bounds(idx, sep_token: int):
+    """Per-row key bounds of a packed token window ``idx`` [B, T] whose documents end with ``sep_token``:
+    (kv_start, q_last), int32 [B, T] each -- position i sees keys kv_start[b, i] <= j <= i, key j is seen by
+    queries j <= i <= q_last[b, j].  A separator is the last token of the document it ends; the first document
+    starts at 0 and the last ends at T - 1.  Fixed-shape device ops only (no sync, no data-dependent shape),
+    so it can sit inside a captured step."""
+    B, T = idx.shape
+    pos = torch.arange(T, device=idx.device, dtype=torch.int32).expand(B, T)
+    sep = idx == sep_token
+    # a document starts right after a separator: position i starts one iff token i - 1 is a separator
+    starts = torch.zeros_like(sep)
+    starts[:, 1:] = sep[:, :-1]
+    kv_start = torch.cummax(torch.where(starts, pos, torch.zeros_like(pos)), dim=1).values
+    # it ends at the next separator at or after i (T - 1 without one): a reversed running minimum
+    ends = torch.where(sep, pos, torch.full_like(pos, T - 1))
+    q_last = -torch.cummax(-ends.flip(1), dim=1).values.flip(1)
+    return kv_start.to(torch.int32).contiguous(), q_last.to(torch.int32).contiguous()
+
+
+def bounds_from_start(kv_start):
+    """q_last [B, T] int32 for any valid ``kv_start`` [B, T] (non-decreasing, 0 <= kv_start[i] <= i): the last
+    query i with kv_start[i] <= j, i.e. searchsorted(kv_start[b], j, right=True) - 1."""
+    B, T = kv_start.shape
+    j = torch.arange(T, device=kv_start.device, dtype=kv_start.dtype).expand(B, T).contiguous()
+    return (torch.searchsorted(kv_start.contiguous(), j, right=True) - 1).to(torch.int32)
+
+
+def _bounds_mask(kv_start):
+    """Boolean visibility [B, 1, T, T] of the bounds (query i, key j): kv_start[b, i] <= j <= i."""
+    T = kv_start.shape[1]
+    j = torch.arange(T, device=kv_start.device)
+    return ((j[None, None, :] >= kv_start[:, :, None]) & (j[None, None, :] <= j[None, :, None])).unsqueeze(1)
+
+
+def _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, qkn=None, kv_start=None):
     """Forward attention over packed qkv -> (qk, o, lse, rstd); ``qk`` is the q / k buffer of the
     pre-pass ([B, T, (H + Hkv) D], None without one), which the backward reads again: rotated (RoPE,
     rope_qk) or, with ``qkn`` = (wq, wk, eps) (QK-norm), normalised per head and then rotated when
@@ -680,7 +714,7 @@ def _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, qkn=None):
     else:
         qk = _ops().rope_qk(qkv, cos, sin, H + 2 * Hkv, H + Hkv, T) if cos is not None else None
     q, k, v = _qkv_heads(qkv, qk, H, Hkv, D)
-    o, lse = _ops().attn_fwd(q, k, v, causal, scale)
+    o, lse = _ops().attn_fwd(q, k, v, causal, scale, kv_start)
     return qk, o, lse, rstd
 
 
@@ -701,7 +735,7 @@ def _qk_norm_bwd(dqkv, qkv, rstd, wq, wk, H, Hkv):
     return None, None
 
 
-def _attn_packed_bwd(do, qkv, qk, o, lse, cfg, cos, sin, delta=None, qkn=None, rstd=None):
+def _attn_packed_bwd(do, qkv, qk, o, lse, cfg, cos, sin, delta=None, qkn=None, rstd=None, kv_start=None, q_last=None):
     """Backward attention -> packed dqkv (for the unrotated qkv: the kernels rotate dq / dk back).
     ``do``: [B, T, H, D] contiguous; ``delta``: rowsum(dO * O) when the caller already holds it.
     Returns (dqkv, dwq, dwk): with ``qkn`` = (wq, wk, eps) one streaming post-pass takes the q / k
@@ -711,7 +745,7 @@ def _attn_packed_bwd(do, qkv, qk, o, lse, cfg, cos, sin, delta=None, qkn=None, r
     dqkv = torch.empty_like(qkv)
     dq, dk, dv = _split_qkv(dqkv, H, Hkv, D)
     _attn_ws(qkv.device)
-    _ops().attn_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, cos, sin, delta)
+    _ops().attn_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, cos, sin, delta, kv_start, q_last)
     dwq = dwk = None
     if qkn is not None:
         dwq, dwk = _qk_norm_bwd(dqkv, qkv, rstd, qkn[0], qkn[1], H, Hkv)
@@ -727,21 +761,21 @@ class _FlashAttnPacked(torch.autograd.Function):
     backward at the llama shape -- the round-2 RoPE A/B record under profiles/ -- and was removed.)"""
 
     @staticmethod
-    def forward(ctx, qkv, H, Hkv, causal, scale, cos, sin, wq=None, wk=None, qk_eps=1e-5):
+    def forward(ctx, qkv, H, Hkv, causal, scale, cos, sin, wq=None, wk=None, qk_eps=1e-5, kv_start=None, q_last=None):
         B, T, W = qkv.shape
         ctx.qkn = (wq, wk, qk_eps) if wq is not None else None  # QK-norm gains (the parameters themselves)
-        qk, o, lse, rstd = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, ctx.qkn)
-        ctx.save_for_backward(qkv, qk, o, lse, cos, sin, rstd)
+        qk, o, lse, rstd = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, ctx.qkn, kv_start)
+        ctx.save_for_backward(qkv, qk, o, lse, cos, sin, rstd, kv_start, q_last)
         ctx.cfg = (H, Hkv, W // (H + 2 * Hkv), causal, scale)
         return o.view(B, T, -1)
 
     @staticmethod
     def backward(ctx, do):
-        qkv, qk, o, lse, cos, sin, rstd = ctx.saved_tensors
+        qkv, qk, o, lse, cos, sin, rstd, kv_start, q_last = ctx.saved_tensors
         dqkv, dwq, dwk = _attn_packed_bwd(do.contiguous().view(o.shape), qkv, qk, o, lse, ctx.cfg, cos, sin,
-                                          qkn=ctx.qkn, rstd=rstd)
+                                          qkn=ctx.qkn, rstd=rstd, kv_start=kv_start, q_last=q_last)
         ctx.qkn = None
-        return dqkv, None, None, None, None, None, None, dwq, dwk, None
+        return dqkv, None, None, None, None, None, None, dwq, dwk, None, None, None
 
 
 class _AttnProjFn(torch.autograd.Function):
@@ -752,12 +786,13 @@ class _AttnProjFn(torch.autograd.Function):
     dim 64 (a wave's 64 output columns are one head).  Same math as _FlashAttnPacked + _LinearFn."""
 
     @staticmethod
-    def forward(ctx, qkv, H, Hkv, causal, scale, cos, sin, w, b, bias_ext, res=None, wq=None, wk=None, qk_eps=1e-5):
+    def forward(ctx, qkv, H, Hkv, causal, scale, cos, sin, w, b, bias_ext, res=None, wq=None, wk=None, qk_eps=1e-5,
+                kv_start=None, q_last=None):
         B, T, W = qkv.shape
         D = W // (H + 2 * Hkv)
         ctx.qkn = (wq, wk, qk_eps) if wq is not None else None  # QK-norm gains (the parameters themselves)
-        qk, o, lse, rstd = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, ctx.qkn)
-        ctx.save_for_backward(qkv, qk, o, lse, cos, sin, rstd)
+        qk, o, lse, rstd = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, ctx.qkn, kv_start)
+        ctx.save_for_backward(qkv, qk, o, lse, cos, sin, rstd, kv_start, q_last)
         ctx.cfg = (H, Hkv, D, causal, scale)
         ctx.w, ctx.b, ctx.bias_ext = w, b, bias_ext
         ctx.has_res = res is not None
@@ -769,7 +804,7 @@ class _AttnProjFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        qkv, qk, o, lse, cos, sin, rstd = ctx.saved_tensors
+        qkv, qk, o, lse, cos, sin, rstd, kv_start, q_last = ctx.saved_tensors
         H, Hkv, D, causal, scale = ctx.cfg
         w, b, qkn = ctx.w, ctx.b, ctx.qkn
         ctx.w = ctx.b = ctx.qkn = None
@@ -801,9 +836,9 @@ class _AttnProjFn(torch.autograd.Function):
             wt = w.t().contiguous()
         do2, delta = _ops().gemm_tn(dy2, wt, None, 6, o2, None, T)
         dqkv, dwq, dwk = _attn_packed_bwd(do2.view(B, T, H, D), qkv, qk, o, lse, ctx.cfg, cos, sin, delta,
-                                          qkn=qkn, rstd=rstd)
+                                          qkn=qkn, rstd=rstd, kv_start=kv_start, q_last=q_last)
         return (dqkv, None, None, None, None, None, None, dw, db, None, (dy if ctx.has_res else None), dwq, dwk,
-                None)
+                None, None, None)
 
 
 # PLLM_AB attn_proj_fused=0: the output projection's backward on hipBLASLt + the attention's delta pre-pass
@@ -827,16 +862,18 @@ def attn_proj_ok(qkv, n_head: int, n_kv_head: int, w, b) -> bool:
 
 def attention_proj(qkv, n_head: int, n_kv_head: int, w, b, causal: bool = True, scale: Optional[float] = None,
                    rope_cos=None, rope_sin=None, bias_grad_external: bool = False, residual=None,
-                   q_norm_weight=None, k_norm_weight=None, qk_norm_eps: float = 1e-5):
+                   q_norm_weight=None, k_norm_weight=None, qk_norm_eps: float = 1e-5, bounds=None):
     """``linear(attention_packed(qkv, ...), w, b)`` (+ ``residual``, added by the GEMM) with the fused
-    backward (see _AttnProjFn)."""
+    backward (see _AttnProjFn).  ``bounds``: see attention_packed."""
     D = qkv.shape[-1] // (n_head + 2 * n_kv_head)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     ext = bool(bias_grad_external and b is not None and not (_TORCH_OPS & {"norm", "act"}))
+    kv_start, q_last = bounds if bounds is not None else (None, None)
     if q_norm_weight is None:
-        return _AttnProjFn.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin, w, b, ext, residual)
+        return _AttnProjFn.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin, w, b, ext, residual,
+                                 None, None, qk_norm_eps, kv_start, q_last)
     return _AttnProjFn.apply(qkv.contiguous(), n_head, n_kv_head, causal, scale, rope_cos, rope_sin, w, b, ext,
-                             residual, q_norm_weight, k_norm_weight, qk_norm_eps)
+                             residual, q_norm_weight, k_norm_weight, qk_norm_eps, kv_start, q_last)
 
 
 _ATTN_WS_MB = [None]
@@ -934,20 +971,26 @@ def qk_norm_packed(qkv, wq, wk, eps: float, n_head: int, n_kv_head: int, cos=Non
 
 def attention_packed(qkv, n_head: int, n_kv_head: int, causal: bool = True, scale: Optional[float] = None,
                      rope_cos: Optional[torch.Tensor] = None, rope_sin: Optional[torch.Tensor] = None,
-                     q_norm_weight=None, k_norm_weight=None, qk_norm_eps: float = 1e-5):
+                     q_norm_weight=None, k_norm_weight=None, qk_norm_eps: float = 1e-5, bounds=None):
     """Causal self-attention over a packed qkv tensor. RoPE (if cos/sin given) is
     applied to the q and k heads first (rotate-half convention); with ``q_norm_weight`` /
-    ``k_norm_weight`` (QK-norm) every q and k head is RMS-normalised over D before that."""
+    ``k_norm_weight`` (QK-norm) every q and k head is RMS-normalised over D before that.
+    ``bounds`` = (kv_start, q_last) (int32 [B, T] each, from ``doc_bounds`` / ``bounds_from_start``; needs
+    ``causal``): position i attends to keys kv_start[b, i] <= j <= i only (document / window masks)."""
     B, T, W = qkv.shape
     D = W // (n_head + 2 * n_kv_head)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    kv_start, q_last = bounds if bounds is not None else (None, None)
+    if bounds is not None and not causal:
+        raise ValueError("attention bounds need causal attention")
     if _hip_op("attn", qkv):
         # RoPE: one rope_qk pre-pass rotates q / k, the backward kernels rotate dq / dk back
         if q_norm_weight is None:
-            return _FlashAttnPacked.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin)
+            return _FlashAttnPacked.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin,
+                                          None, None, qk_norm_eps, kv_start, q_last)
         # QK-norm: qk_norm_rope is that pre-pass, qk_norm_bwd_ a post-pass over dqkv
         return _FlashAttnPacked.apply(qkv.contiguous(), n_head, n_kv_head, causal, scale, rope_cos, rope_sin,
-                                      q_norm_weight, k_norm_weight, qk_norm_eps)
+                                      q_norm_weight, k_norm_weight, qk_norm_eps, kv_start, q_last)
     if q_norm_weight is not None:
         q, k = qk_norm_packed(qkv, q_norm_weight, k_norm_weight, qk_norm_eps, n_head, n_kv_head, rope_cos, rope_sin)
         v = _split_qkv(qkv, n_head, n_kv_head, D)[2]
@@ -958,10 +1001,14 @@ def attention_packed(qkv, n_head: int, n_kv_head: int, causal: bool = True, scal
     if _stock("attn") and qkv.is_cuda:
         # stock-PyTorch baseline path (SDPA), used only by the explicit torch backend
         qh, kh, vh = (t.transpose(1, 2) for t in (q, k, v))
-        o = F.scaled_dot_product_attention(qh, kh, vh, is_causal=causal, scale=scale,
-                                           enable_gqa=(n_kv_head != n_head))
+        if bounds is not None:  # the bounds as a boolean mask (it includes the causal triangle)
+            o = F.scaled_dot_product_attention(qh, kh, vh, attn_mask=_bounds_mask(kv_start), scale=scale,
+                                               enable_gqa=(n_kv_head != n_head))
+        else:
+            o = F.scaled_dot_product_attention(qh, kh, vh, is_causal=causal, scale=scale,
+                                               enable_gqa=(n_kv_head != n_head))
         return o.transpose(1, 2).reshape(B, T, n_head * D)
-    o, _ = ref.attention(q, k, v, causal=causal, scale=scale)
+    o, _ = ref.attention(q, k, v, causal=causal, scale=scale, bounds=bounds)
     return o.reshape(B, T, n_head * D)
 
 

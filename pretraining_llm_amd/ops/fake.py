@@ -174,7 +174,7 @@ def register() -> None:
                 logits.new_empty((B,), dtype=torch.float32))
 
     @_reg("attn_fwd")
-    def _(q, k, v, causal, scale):
+    def _(q, k, v, causal, scale, kv_start=None):
         B, T, H, _ = q.shape
         return [q.new_empty(q.shape), q.new_empty((B, H, T), dtype=f32)]
 
@@ -183,7 +183,8 @@ def register() -> None:
         return q.new_empty(q.shape)
 
     @_reg("attn_bwd")
-    def _(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, rope_cos=None, rope_sin=None, delta=None):
+    def _(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, rope_cos=None, rope_sin=None, delta=None,
+          kv_start=None, q_last=None):
         return None
 
     @_reg("gemv")

@@ -44,8 +44,19 @@ def qk_norm(x, weight, eps: float):
     return rms_norm(x, weight, eps)
 
 
-def attention(q, k, v, causal: bool = True, scale: Optional[float] = None):
-    """q: [B,T,H,D], k/v: [B,S,Hkv,D] -> out [B,T,H,D], lse [B,H,T] (natural log)."""
+def _bounds_visible(bounds, causal: bool, T: int, S: int):
+    """[B, 1, T, S] lower limit of per-row key bounds (kv_start, q_last): kv_start[b, i] <= j (the upper limit
+    j <= i is the caller's causal mask)."""
+    if not causal or S != T:
+        raise ValueError("attention bounds need causal attention with S == T")
+    kv_start = bounds[0]
+    j = torch.arange(S, device=kv_start.device)
+    return (j[None, None, :] >= kv_start[:, :, None]).unsqueeze(1)
+
+
+def attention(q, k, v, causal: bool = True, scale: Optional[float] = None, bounds=None):
+    """q: [B,T,H,D], k/v: [B,S,Hkv,D] -> out [B,T,H,D], lse [B,H,T] (natural log).
+    ``bounds`` = (kv_start, q_last), int [B, T] each: query i sees keys kv_start[b, i] <= j <= i only."""
     B, T, H, D = q.shape
     S, Hkv = k.shape[1], k.shape[2]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
@@ -62,13 +73,15 @@ def attention(q, k, v, causal: bool = True, scale: Optional[float] = None):
         off = S - T
         mask = torch.ones(T, S, dtype=torch.bool, device=q.device).tril(diagonal=off)
         s = s.masked_fill(~mask, float("-inf"))
+    if bounds is not None:
+        s = s.masked_fill(~_bounds_visible(bounds, causal, T, S), float("-inf"))
     lse = torch.logsumexp(s, dim=-1)                    # B,H,T
     p = torch.exp(s - lse.unsqueeze(-1))
     o = torch.matmul(p, vf)                             # B,H,T,D
     return o.transpose(1, 2).to(q.dtype), lse
 
 
-def attention_bwd(do, q, k, v, o, lse, causal: bool = True, scale: Optional[float] = None):
+def attention_bwd(do, q, k, v, o, lse, causal: bool = True, scale: Optional[float] = None, bounds=None):
     """Flash-style backward of one attention block given the row statistics of the WHOLE
     softmax (``lse`` [B,H,T], natural log, and the final output ``o``), so partial key
     blocks (ring / context parallel) produce exact partial gradients.
@@ -84,6 +97,8 @@ def attention_bwd(do, q, k, v, o, lse, causal: bool = True, scale: Optional[floa
     if causal:
         mask = torch.ones(T, S, dtype=torch.bool, device=q.device).tril(diagonal=S - T)
         s = s.masked_fill(~mask, float("-inf"))
+    if bounds is not None:
+        s = s.masked_fill(~_bounds_visible(bounds, causal, T, S), float("-inf"))
     p = torch.exp(s - lse.float().unsqueeze(-1))
     dv = torch.matmul(p.transpose(-1, -2), dof)                              # B,H,S,D
     dp = torch.matmul(dof, vf.transpose(-1, -2))

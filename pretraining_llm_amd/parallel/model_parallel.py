@@ -306,6 +306,9 @@ def parallelize_gpt(model, pg: ParallelGroups):
     if pg.tp > 1 and pg.cp > 1 and pg.sequence_parallel:
         raise ValueError("sequence_parallel with context parallelism is not supported (use tp x cp without SP)")
     cfg = model.config
+    if cfg.doc_mask and (pg.tp > 1 or pg.cp > 1):
+        # the sharded attention paths (TPAttention, ring / Ulysses) take no per-row key bounds
+        raise ValueError(f"doc_mask is not supported with tensor or context parallelism (tp={pg.tp}, cp={pg.cp})")
     if cfg.qk_norm and (pg.tp > 1 or pg.cp > 1):
         # TP: the replicated gains see only the local heads, so their gradients would need a TP-group sum
         # (sync_replicated_grads covers sequence parallelism only); CP: ring / Ulysses attention take their own path

@@ -43,7 +43,8 @@ from .optim import FlatAdamW, no_decay_1d
 def model_config_from(cfg: dict) -> ModelConfig:
     preset = cfg.get("model_preset")
     dims = {k: cfg[k] for k in ("vocab_size", "context_length", "n_embed", "n_head", "n_blocks") if k in cfg}
-    extra = {k: cfg[k] for k in ("n_kv_head", "ffn_hidden", "activation_checkpointing", "qk_norm", "qk_norm_eps")
+    extra = {k: cfg[k] for k in ("n_kv_head", "ffn_hidden", "activation_checkpointing", "qk_norm", "qk_norm_eps",
+                                  "doc_mask", "doc_sep_token")
              if cfg.get(k) is not None}
     if preset:
         mc = get_preset(preset)
@@ -56,6 +57,10 @@ def model_config_from(cfg: dict) -> ModelConfig:
 def check_parallel_config(cfg: dict) -> None:
     """Combinations the model-parallel layouts do not cover, rejected before any process group exists."""
     tp, cp = int(cfg.get("tp_size", 1)), int(cfg.get("cp_size", 1))
+    if (tp > 1 or cp > 1) and model_config_from(cfg).doc_mask:
+        raise ValueError(f"doc_mask is not supported with tensor or context parallelism (tp_size={tp}, "
+                         f"cp_size={cp}): the sharded attention paths (sequence-parallel, ring, Ulysses) take no "
+                         "per-row key bounds")
     if (tp > 1 or cp > 1) and model_config_from(cfg).qk_norm:
         raise ValueError(f"qk_norm is not supported with tensor or context parallelism (tp_size={tp}, "
                          f"cp_size={cp}): under TP the replicated gains see only the local heads and their "
