@@ -1190,6 +1190,29 @@ TORCH_LIBRARY(pllm, m) {
   m.def("wgrad(Tensor dy, Tensor x, Tensor(a!)? out_acc=None, Tensor(b!)? bias_acc=None, bool overwrite=False) -> Tensor");
   m.def("gemm_tn(Tensor a, Tensor b, Tensor? bias, int epi, Tensor? aux=None, Tensor(a!)? bias_acc=None, int T=0) -> (Tensor, Tensor)");
   m.def("gemm_uses_pp(int K, int epi) -> bool", [](int64_t K, int64_t epi) { return pllm::gemm_uses_pp((int)K, (int)epi, 16); });
+  // read-only views of the dispatch under the current settings (the tests assert the arm a case was written for):
+  // gemm_plan -> [ping-pong kernel, quadrant epilogues, workgroups, tile rows, tile columns, column-sum
+  // partial rows of epi 3 / 4]; N as gemm_tn takes it (epi 7: F)
+  m.def("gemm_plan(int M, int N, int K, int epi, int T=0) -> int[]",
+        [](int64_t M, int64_t N, int64_t K, int64_t epi, int64_t T) {
+          const bool pp = pllm::gemm_uses_pp((int)K, (int)epi, (int)T);
+          const int64_t tm = (M + 255) / 256, tn = pp && epi == 7 ? (N + 127) / 128 : (N + 255) / 256;
+          return std::vector<int64_t>{pp, pp && pllm::gemm_pp_quad_epilogue((int)K, (int)epi),
+                                      std::min<int64_t>(tm * tn, pllm::gemm_grid_cap()), tm, tn,
+                                      pllm::gemm_colsum_groups((int)M, (int)K)};
+        });
+  // wgrad_plan -> [arm (wgrad_arm: 0 / 1 one-barrier kernel 16x16x32 / 32x32x16, 2 ping-pong, 3 hybrid), S,
+  // slice (tokens), then the hybrid form's whole tiles, sliced tiles, their slice count and K-tiles per slice
+  // (zeros on the other arms)]
+  m.def("wgrad_plan(int M, int P, int Q, bool out_f32, bool bias) -> int[]",
+        [](int64_t M, int64_t P, int64_t Q, bool of32, bool bias) {
+          int S = 1, slice = 1, full = 0, rem = 0, hs = 0, skt = 0;
+          pllm::wgrad_plan((int)M, (int)P, (int)Q, &S, &slice);
+          const int arm = pllm::wgrad_arm((int)M, (int)P, (int)Q, of32, bias);
+          if (arm != 3 || !pllm::wgrad_hy_plan((int)M, (int)P, (int)Q, pllm::gemm_grid_cap(), &full, &rem, &hs, &skt))
+            full = rem = hs = skt = 0;
+          return std::vector<int64_t>{arm, S, slice, full, rem, hs, skt};
+        });
   m.def("gemm_set_config(int mfma, int group_m, int phased=-1, int reserve_cus=-1, int persistent=-1) -> ()",
         [](int64_t mf, int64_t gm, int64_t ph, int64_t rc, int64_t pe) {
           pllm::gemm_set_config((int)mf, (int)gm, (int)ph, (int)rc, (int)pe);

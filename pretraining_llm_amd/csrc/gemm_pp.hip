@@ -837,7 +837,8 @@ int gemm_pp_colsum_groups(int M, int K) { return (gemm_pp_quad_epilogue(K, 3) ? 
 // quadrant epilogues at K >= 2048, except EPI 5 (aux too large for the LDS) and EPI 1 (the GELU's
 // VALU work in the LOAD segments: 1410 vs 1344 us for the end-of-tile form + hipBLASLt at the llama
 // shape 32768 x 11008 x 2048, gpurun_out/r4pp7_bench.jsonl)
-bool gemm_pp_quad_epilogue(int K, int epi) { return K >= 2048 && epi != 5 && epi != 1; }
+// (EPI 7 has no quadrant form either: its instantiation below is always the end-of-tile one)
+bool gemm_pp_quad_epilogue(int K, int epi) { return K >= 2048 && epi != 5 && epi != 1 && epi != 7; }
 
 void gemm_tn_pp(const GemmArgs& a, int epi, int ctas, hipStream_t st) {
   const int nt = epi == 7 ? 128 : PT;

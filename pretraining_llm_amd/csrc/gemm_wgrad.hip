@@ -371,16 +371,25 @@ int64_t wgrad_ws_floats(int M, int P, int Q, bool out_f32, bool bias) {
   return S > 1 ? (int64_t)S * P * Q : 0;
 }
 
+int wgrad_arm(int M, int P, int Q, bool out_f32, bool bias) {
+  if (wgrad_use_hy(M, P, Q, out_f32, bias)) return 3;
+  int S, slice;
+  wgrad_plan(M, P, Q, &S, &slice);
+  if (g_wgrad_pp && out_f32 && wgrad_pp_supported(M, P, Q, S, slice)) return 2;
+  return (g_wgrad_mfma != 0 ? g_wgrad_mfma : (P >= 16384 ? 32 : 16)) == 16 ? 0 : 1;
+}
+
 bool wgrad(const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P, int Q, float* part, void* out,
            bool out_f32, bool accumulate, hipStream_t st, float* bpart, void* bout, bool bout_f32) {
-  if (wgrad_use_hy(M, P, Q, out_f32, bpart != nullptr && bout != nullptr)) {
+  const int arm = wgrad_arm(M, P, Q, out_f32, bpart != nullptr && bout != nullptr);
+  if (arm == 3) {
     wgrad_pp_hy(dy, lda, x, ldb, M, P, Q, part, (float*)out, accumulate, gemm_grid_cap(), st);
     return false;
   }
   int S, slice;
   wgrad_plan(M, P, Q, &S, &slice);
   const int ntiles = ((P + BT - 1) / BT) * ((Q + BT - 1) / BT);
-  if (g_wgrad_pp && out_f32 && wgrad_pp_supported(M, P, Q, S, slice)) {
+  if (arm == 2) {
     const bool fb = bpart != nullptr && bout != nullptr;
     wgrad_pp(dy, lda, x, ldb, M, P, Q, S, slice, part, (float*)out, accumulate, fb ? bpart : nullptr,
              gemm_grid_cap(), st);
@@ -396,7 +405,7 @@ bool wgrad(const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P
     }
     return fb;
   }
-  const int mfma = g_wgrad_mfma != 0 ? g_wgrad_mfma : (P >= 16384 ? 32 : 16);
+  const int mfma = arm == 0 ? 16 : 32;
   // the bias gradient rides along only on the 16x16x32 kernel (see wgrad_kernel)
   const bool fuse_b = bpart != nullptr && bout != nullptr && mfma == 16;
   float* const bp = fuse_b ? bpart : nullptr;

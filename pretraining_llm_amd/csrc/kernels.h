@@ -173,6 +173,9 @@ void wgrad_pp_hy(const void* dy, int64_t lda, const void* x, int64_t ldb, int M,
 void wgrad_set_hy(int on);  // A/B: hybrid weight gradients where they apply
 // workspace floats wgrad() needs for this call (slice slabs or stream-K pieces)
 int64_t wgrad_ws_floats(int M, int P, int Q, bool out_f32, bool bias);
+// the kernel wgrad() runs for this call under the current settings: 0 / 1 gemm_wgrad.hip's kernel with
+// 16x16x32 / 32x32x16 MFMAs, 2 the ping-pong kernel, 3 its hybrid form
+int wgrad_arm(int M, int P, int Q, bool out_f32, bool bias);
 bool wgrad(const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P, int Q, float* part, void* out,
            bool out_f32, bool accumulate, hipStream_t st, float* bpart = nullptr, void* bout = nullptr,
            bool bout_f32 = false);
