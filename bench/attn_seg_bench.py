@@ -5,11 +5,13 @@ one process.  One JSON line per shape: per-round us of each arm, and median rati
 Arms:  plain     no bounds (the existing instantiations)
        one_doc   bounds all zero: the cost of the extra compare and the bound loads, nothing skipped
        docN      fixed-seed random document lengths of mean N (exponential, at least 1 token), per batch row
+       windowW   a sliding window of W keys (ops.window_bounds), with ``--window W,...``
 
 ``--plain-only`` times the plain arm alone (it then runs on a build without the bounds, for build-to-build
 comparisons: run the two builds alternately, one process each).
 
-usage: python bench/attn_seg_bench.py [--configs BxHxTxD[xHkv],...] [--rounds 7] [--doc-len 256,512] [--plain-only]"""
+usage: python bench/attn_seg_bench.py [--configs BxHxTxD[xHkv],...] [--rounds 7] [--doc-len 256,512] [--window 512,...]
+       [--plain-only]"""
 import argparse
 import json
 import math
@@ -54,6 +56,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--doc-len", default="256,512")
+    ap.add_argument("--window", default="")
     ap.add_argument("--plain-only", action="store_true")
     args = ap.parse_args()
     from pretraining_llm_amd.ops import _lib
@@ -77,6 +80,8 @@ def main():
             arms["one_doc"] = ops.doc_bounds(torch.zeros(B, T, dtype=torch.long, device=dev), 1)
             for n in (int(s) for s in args.doc_len.split(",") if s):
                 arms[f"doc{n}"] = ops.doc_bounds(random_docs(B, T, n, 1234 + n).to(dev), 1)
+            for w in (int(s) for s in args.window.split(",") if s):
+                arms[f"window{w}"] = ops.window_bounds(B, T, w, dev)
         fns, vis = {}, {}
         for name, bnd in arms.items():
             extra_f = () if bnd is None else (bnd[0],)

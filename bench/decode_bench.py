@@ -3,10 +3,12 @@
 GPT-2 small (random init, bf16): prefill a ``--prompt``-token prompt for ``B`` sequences, then
 decode ``--new`` tokens greedily, eager (one launch per kernel) vs one hipGraph replay per
 token (``DecodeGraph``).  Also times the decode-attention kernel alone against the flash
-forward kernel run with a single query row (what decode used before the split-KV kernel).
+forward kernel run with a single query row (what decode used before the split-KV kernel), and
+with a sliding window (``attn_decode(window=)``: S = 8192 cached keys, D = 128, B in {1, 64}, window 0
+and 1024, interleaved round by round).  ``--kernels-only`` stops after the kernel arms.
 Prints one JSON line per configuration.
 
-usage: python bench/decode_bench.py [--batches 1,16,64] [--prompt 128] [--new 256]
+usage: python bench/decode_bench.py [--batches 1,16,64] [--prompt 128] [--new 256] [--kernels-only]
 """
 from __future__ import annotations
 
@@ -39,6 +41,8 @@ def main():
     ap.add_argument("--batches", default="1,16,64")
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--new", type=int, default=256)
+    ap.add_argument("--kernels-only", action="store_true")
+    ap.add_argument("--rounds", type=int, default=7)
     args = ap.parse_args()
     import torch
     from pretraining_llm_amd import ops
@@ -59,6 +63,32 @@ def main():
         print(json.dumps({"kernel": "attn_decode", "B": B, "S": S, "H": H, "D": D, "decode_us": round(t_dec * 1e6, 2),
                           "flash_fwd_1row_us": round(t_fa * 1e6, 2),
                           "decode_kv_GBps": round(kv_bytes / t_dec / 1e9, 1)}), flush=True)
+
+    # sliding window: a local layer reads the last `window` rows of the count instead of all S
+    import statistics
+    for B in (1, 64):
+        S, H, Hkv, D = 8192, 16, 16, 128
+        q = torch.randn(B, 1, H, D, device=dev, dtype=torch.bfloat16)
+        k = torch.randn(B, S, Hkv, D, device=dev, dtype=torch.bfloat16)
+        v = torch.randn(B, S, Hkv, D, device=dev, dtype=torch.bfloat16)
+        n = torch.full((B,), S, dtype=torch.int32, device=dev)
+        sc = 1.0 / math.sqrt(D)
+        times = {0: [], 1024: []}
+        for rnd in range(args.rounds + 1):
+            for w in times:
+                t = timeit(lambda w=w: torch.ops.pllm.attn_decode(q, k, v, sc, n, w), iters=200)
+                if rnd > 0:  # round 0 is warm-up
+                    times[w].append(t)
+        med = {w: statistics.median(ts) for w, ts in times.items()}
+        print(json.dumps({"kernel": "attn_decode_window", "B": B, "S": S, "H": H, "Hkv": Hkv, "D": D,
+                          **{f"window{w}_us": [round(t * 1e6, 2) for t in ts] for w, ts in times.items()},
+                          **{f"window{w}_median_us": round(med[w] * 1e6, 2) for w in times},
+                          "window0_kv_GBps": round(2 * B * S * Hkv * D * 2 / med[0] / 1e9, 1),
+                          "window1024_kv_GBps": round(2 * B * 1024 * Hkv * D * 2 / med[1024] / 1e9, 1),
+                          "window1024_over_window0": round(med[1024] / med[0], 3)}), flush=True)
+        del q, k, v
+    if args.kernels_only:
+        return
 
     torch.manual_seed(0)
     cfg = get_preset(args.model)

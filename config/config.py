@@ -96,6 +96,8 @@ default_config = {
     'qk_norm_eps': None,
     'doc_mask': None,                 # True: a token attends only to its own document of the packed window (None -> the preset's)
     'doc_sep_token': None,            # the token that ends a document (None -> the preset's: 50256, the data pipeline's end-of-text)
+    'sliding_window': None,           # W: a local layer's query sees its last W keys, itself included (None -> the preset's)
+    'sliding_window_pattern': None,   # 0: every layer local; n >= 2: every n-th layer global (None -> the preset's)
     'override_preset_dims': False,    # with model_preset: the dims above (n_embed, n_head, n_blocks, ...) override the preset's
     'tuned_gemms': True,              # GPU: load the shipped TunableOp GEMM selections (pretraining_llm_amd/tuning/)
     'tp_size': 1,                     # tensor parallelism: heads / FFN columns sharded (parallel/model_parallel.py)

@@ -21,6 +21,9 @@
 //  * the key count can come from a device scalar (`seqlen`; or one count per sequence for
 //    continuous batching, where every slot of the batch sits at its own position), so a decode step
 //    can be captured once in a hipGraph and replayed at every position.
+//  * a sliding window (`window` > 0, a host constant of the layer) limits the keys to the last `window`
+//    rows [max(0, S - window), S) of the count: a local layer streams `window` cache rows per token, not
+//    the whole context, and the count stays on the device.
 #include "common.h"
 #include "kernels.h"
 
@@ -36,8 +39,10 @@ __global__ __launch_bounds__(NT) void attn_decode_kernel(DecodeArgs a) {
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int dp = t % LPR, ks = t / LPR;
   const int S = a.seqlen ? a.seqlen[a.seqlen_per_row ? b : 0] : a.S;
-  const int chunk = (S + a.splits - 1) / a.splits;
-  const int k0 = split * chunk, k1 = min(S, k0 + chunk);
+  // sliding window: only the last `window` keys [first, S) are visible; the splits partition that range
+  const int first = a.window > 0 ? max(0, S - a.window) : 0;
+  const int chunk = (S - first + a.splits - 1) / a.splits;
+  const int k0 = first + split * chunk, k1 = min(S, k0 + chunk);
 
   // q fragments of the G heads of this group, pre-scaled by scale*log2(e)
   float q[G][8];
@@ -209,6 +214,7 @@ bool attn_decode_supported(int D, int group) {
 }
 
 int attn_decode_splits(int B, int Hkv, int S_max) {
+  // (S_max: the most keys one sequence can see -- min(cache rows, window) under a sliding window)
   // >= ~2 workgroups per CU over the whole grid, >= 64 keys per split
   const int want = (512 + B * Hkv - 1) / (B * Hkv);
   const int cap = (S_max + 63) / 64;

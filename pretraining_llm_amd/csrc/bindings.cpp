@@ -1031,8 +1031,10 @@ std::vector<Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, 
 
 // single-query decode attention: q [B, 1, H, D], k/v [B, S, Hkv, D] views of a KV cache
 // (any batch/row strides).  ``seqlen``: optional int32 device scalar overriding S (the
-// number of valid cache rows) so a captured decode step replays at every position.
-Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, double scale, const c10::optional<Tensor>& seqlen) {
+// number of valid cache rows) so a captured decode step replays at every position.  ``window`` > 0
+// (sliding-window attention, a host constant): only the last ``window`` keys of the count are read.
+Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, double scale, const c10::optional<Tensor>& seqlen,
+                   int64_t window) {
   const int64_t D = q.size(3);
   check_head_view(q, "q", D);
   check_head_view(k, "k", D);
@@ -1043,6 +1045,7 @@ Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, double sca
               "attn_decode: k/v shape");
   TORCH_CHECK(H % Hkv == 0 && pllm::attn_decode_supported((int)D, (int)(H / Hkv)),
               "attn_decode: head dim 32/64/128 and group size 1/2/4/8 supported");
+  TORCH_CHECK(window >= 0, "attn_decode: window must be >= 0 (0 = no window)");
   Tensor o = at::empty({B, 1, H, D}, q.options());
   DecodeArgs a{};
   a.q = (const uint16_t*)q.data_ptr();
@@ -1062,7 +1065,9 @@ Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, double sca
     a.seqlen = seqlen->data_ptr<int>();
     a.seqlen_per_row = seqlen->numel() == B && B > 1;
   }
-  a.splits = pllm::attn_decode_splits((int)B, (int)Hkv, (int)S);
+  // a window at least as long as the buffer never bites: the kernel then runs exactly as without one
+  a.window = window > 0 && window < S ? (int)window : 0;
+  a.splits = pllm::attn_decode_splits((int)B, (int)Hkv, a.window ? a.window : (int)S);
   Tensor part_o, part_lse;
   if (a.splits > 1) {
     part_o = at::empty({B, H, a.splits, D}, q.options().dtype(at::kFloat));
@@ -1246,7 +1251,7 @@ TORCH_LIBRARY(pllm, m) {
   m.def("sample(Tensor logits, float temperature, int seed) -> Tensor");
   m.def("sample_rows(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor min_p, Tensor seed, Tensor step) -> (Tensor tokens, Tensor kept, Tensor min_kept)");
   m.def("attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, Tensor? kv_start=None) -> Tensor[]");
-  m.def("attn_decode(Tensor q, Tensor k, Tensor v, float scale, Tensor? seqlen=None) -> Tensor");
+  m.def("attn_decode(Tensor q, Tensor k, Tensor v, float scale, Tensor? seqlen=None, int window=0) -> Tensor");
   m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, Tensor? delta=None, Tensor? kv_start=None, Tensor? q_last=None) -> ()");
 }
 

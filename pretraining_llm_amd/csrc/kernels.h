@@ -30,6 +30,7 @@ struct DecodeArgs {
   int B, H, Hkv, S, D, splits;
   int64_t q_sb, q_sh, k_sb, k_st, k_sh, v_sb, v_st, v_sh, o_sb, o_sh;
   float scale_log2;
+  int window;                // sliding window: only the last `window` keys of the count are read (0 = all)
 };
 
 struct AttnBwdArgs {

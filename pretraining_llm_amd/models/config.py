@@ -49,6 +49,13 @@ class ModelConfig:
     # ends).  No parameters; positions are unchanged; KV-cache generation treats its context as one document
     doc_mask: bool = False
     doc_sep_token: int = 50256
+    # Sliding-window attention (Mistral / Gemma-2/3 / gpt-oss): in a local layer query i sees the W = sliding_window
+    # keys max(0, i - W + 1) <= j <= i, itself included (None: off).  sliding_window_pattern 0 makes every layer
+    # local; n >= 2 makes layer l (0-based) global iff (l + 1) % n == 0 (2 alternates, 6 is Gemma-3).  Architecture,
+    # not a training trick: training, recompute and KV-cache generation and the servers all apply it.  No parameters;
+    # positions are unchanged; with doc_mask a local layer sees the intersection of window and document
+    sliding_window: Optional[int] = None
+    sliding_window_pattern: int = 0
     init: str = "gpt2"                      # gpt2 | torch_default
     init_std: float = 0.02
     # True / False, a float fraction of the blocks, or "auto": checkpoint only as many blocks as
@@ -67,6 +74,13 @@ class ModelConfig:
         if self.doc_mask and not 0 <= self.doc_sep_token < self.vocab_size:
             raise ValueError(f"doc_mask: doc_sep_token={self.doc_sep_token} is outside the vocabulary "
                              f"[0, {self.vocab_size})")
+        if self.sliding_window is not None and self.sliding_window < 1:
+            raise ValueError(f"sliding_window={self.sliding_window}: a window holds at least the query itself (>= 1)")
+        if self.sliding_window_pattern < 0 or self.sliding_window_pattern == 1:
+            raise ValueError(f"sliding_window_pattern={self.sliding_window_pattern}: 0 (every layer local) or n >= 2 "
+                             "(every n-th layer global)")
+        if self.sliding_window_pattern and self.sliding_window is None:
+            raise ValueError(f"sliding_window_pattern={self.sliding_window_pattern} needs a sliding_window")
         if self.ffn_hidden is None:
             if self.mlp == "swiglu":
                 h = int(2 * (4 * self.n_embed) / 3)
@@ -77,6 +91,15 @@ class ModelConfig:
     @property
     def head_dim(self) -> int:
         return self.n_embed // self.n_head
+
+    def layer_window(self, layer_idx: int) -> Optional[int]:
+        """The sliding window of layer ``layer_idx`` (0-based): None for a global layer or without a window."""
+        if self.sliding_window is None:
+            return None
+        n = self.sliding_window_pattern
+        if n >= 2 and (layer_idx + 1) % n == 0:
+            return None
+        return self.sliding_window
 
     def _default_ffn(self, n_embed: int, mlp: str) -> int:
         if mlp == "swiglu":
@@ -187,6 +210,11 @@ PRESETS = {
                                  ffn_hidden=5504),
     "llama-tiny": lambda: _llama(vocab_size=512, context_length=128, n_embed=128, n_head=4, n_blocks=2,
                                  n_kv_head=2, ffn_hidden=256),
+    # the same two with sliding-window attention: local / global layers alternating, 3 local : 1 global
+    "llama-1.3b-swa": lambda: _llama(vocab_size=50304, context_length=2048, n_embed=2048, n_head=16, n_blocks=24,
+                                     ffn_hidden=5504, sliding_window=512, sliding_window_pattern=4),
+    "llama-tiny-swa": lambda: _llama(vocab_size=512, context_length=128, n_embed=128, n_head=4, n_blocks=2,
+                                     n_kv_head=2, ffn_hidden=256, sliding_window=32, sliding_window_pattern=2),
     # the same two with QK-norm
     "llama-1.3b-qknorm": lambda: _llama(vocab_size=50304, context_length=2048, n_embed=2048, n_head=16, n_blocks=24,
                                         ffn_hidden=5504, qk_norm=True),

@@ -78,6 +78,9 @@ class Attention(nn.Module):
         qkv_out = (cfg.n_head + 2 * cfg.n_kv_head) * cfg.head_dim
         self.qkv = nn.Linear(C, qkv_out, bias=cfg.bias and cfg.arch != "ref")
         self.proj = nn.Linear(C, C, bias=cfg.bias) if cfg.attn_out_proj else None
+        # sliding-window attention: this layer's window (None: a global layer).  Training gets it as ``bounds``
+        # from GPT._trunk; the KV-cache paths below apply it themselves
+        self.window = cfg.layer_window(layer_idx)
         self.qk_norm = bool(cfg.qk_norm)
         if self.qk_norm:  # only then: state dicts of models without QK-norm keep their keys
             self.q_norm, self.k_norm = HeadNorm(cfg.head_dim), HeadNorm(cfg.head_dim)
@@ -93,8 +96,8 @@ class Attention(nn.Module):
 
     def forward_res(self, x, rope=None, fuse_out_bias: bool = False, residual=None, bounds=None):
         """(y + residual, True) when the fused projection adds the block's residual stream in its GEMM
-        (ops.resid_gemm_ok), else (y, False) and the caller's norm adds it.  ``bounds``: the window's
-        per-row key bounds (ops.doc_bounds) under document masking."""
+        (ops.resid_gemm_ok), else (y, False) and the caller's norm adds it.  ``bounds``: the per-row key
+        bounds of this layer (ops.doc_bounds under document masking, ops.window_bounds in a sliding-window layer)."""
         qkv = ops.linear(x, self.qkv.weight, self.qkv.bias)
         cos, sin = rope if rope is not None else (None, None)
         if self.proj is not None and ops.attn_proj_ok(qkv, self.n_head, self.n_kv_head, self.proj.weight,
@@ -130,7 +133,16 @@ class Attention(nn.Module):
             q = ops.apply_rope(q, cos, sin, pos)
             k = ops.apply_rope(k, cos, sin, pos)
         kc, vc = cache.update(layer_idx, k, v, pos)
-        y = ops.attention(q.contiguous(), kc, vc, causal=True)
+        W = self.window
+        if W is not None and T > 1 and pos > 0:
+            raise NotImplementedError(f"sliding_window: a cached step of T={T} > 1 tokens at pos={pos} > 0 (chunked "
+                                      "prefill) is not supported in a local layer")
+        if W is not None and T > 1 and W < T:  # prefill from position 0 (S == T): per-row key bounds
+            y = ops.attention(q.contiguous(), kc, vc, causal=True, kv_start=ops.window_bounds(B, T, W, q.device)[0])
+        elif W is not None and T == 1:  # one token: the last W rows of the cache view
+            y = ops.attention(q.contiguous(), kc[:, max(0, pos + 1 - W):], vc[:, max(0, pos + 1 - W):], causal=True)
+        else:
+            y = ops.attention(q.contiguous(), kc, vc, causal=True)
         y = y.reshape(B, T, H * D)
         if self.proj is not None:
             y = ops.linear(y, self.proj.weight, self.proj.bias)
@@ -174,7 +186,8 @@ class Attention(nn.Module):
             else:
                 cache.k[layer_idx].index_copy_(1, pos_t, k)
                 cache.v[layer_idx].index_copy_(1, pos_t, v)
-        y = ops.attention_decode(q.contiguous(), cache.k[layer_idx], cache.v[layer_idx], seqlen=len_t)
+        y = ops.attention_decode(q.contiguous(), cache.k[layer_idx], cache.v[layer_idx], seqlen=len_t,
+                                 window=self.window)
         y = y.reshape(B, 1, H * D)
         if self.proj is not None:
             y = ops.linear(y, self.proj.weight, self.proj.bias)
@@ -242,7 +255,7 @@ class Block(nn.Module):
 
     def forward(self, x, residual=None, rope=None, x_bias=None, fuse_mlp_out_bias: bool = False, bounds=None):
         """(x, residual) -> (mlp_out, residual_after_attn); the caller's next norm adds them.
-        ``bounds``: per-row key bounds of the attention (document masking), else None.
+        ``bounds``: per-row key bounds of the attention (document masking, sliding window), else None.
 
         Fused bias gradients (HIP path): ``x_bias`` is the bias of the layer that produced x (the
         previous block's MLP down projection), emitted by ln1's backward; the attention output
@@ -254,7 +267,7 @@ class Block(nn.Module):
         # the output projections may add the residual stream in their GEMMs (ops.resid_gemm_ok; the reference's
         # x + attn(ln1(x)) / x + mlp(ln2(x)), /root/reference/src/models/transformer_block.py:44,46): then the
         # next norm gets the stream itself (residual None) and the block returns (stream, None)
-        if bounds is not None:  # (doc_mask is rejected under tensor / context parallelism: the dense Attention)
+        if bounds is not None:  # (doc_mask / sliding_window are rejected under tensor / context parallelism: the dense Attention)
             a, a_res = self.attn.forward_res(h, rope, fuse, res, bounds=bounds)
         elif hasattr(self.attn, "forward_res"):
             a, a_res = self.attn.forward_res(h, rope, fuse, res)
@@ -303,9 +316,9 @@ class Block(nn.Module):
                                      kv_written=kv is not None)
         return self._mlp_infer(a, res)
 
-    def forward_embedding(self, x, residual=None, rope=None):
+    def forward_embedding(self, x, residual=None, rope=None, bounds=None):
         h, res = self.ln1(x, residual)
-        a = self.attn(h, rope)
+        a = self.attn(h, rope, bounds=bounds) if bounds is not None else self.attn(h, rope)
         h2, res2 = self.ln2(a, res)
         return self.mlp.forward_embedding(h2), res2
 
@@ -494,14 +507,24 @@ class GPT(nn.Module):
             if pg is not None and pg.model_parallel:
                 raise ValueError("doc_mask is not supported with tensor or context parallelism")
             bounds = ops.doc_bounds(idx, self.config.doc_sep_token)
+        # sliding window: local layers take the intersection of window and document; a window that covers the
+        # whole sequence does not bite, and local layers then run as global ones (two bounds per call at most)
+        local = bounds
+        W = self.config.sliding_window
+        if W is not None:
+            if pg is not None and pg.model_parallel:
+                raise ValueError("sliding_window is not supported with tensor or context parallelism")
+            if W < idx.shape[1]:
+                local = ops.window_bounds(idx.shape[0], idx.shape[1], W, idx.device, doc=bounds)
         res = None
         n_ckpt = self.checkpointed_blocks(idx) if self.training and torch.is_grad_enabled() else 0
         x_bias = None  # bias of the layer that produced x (fused into the next norm's backward)
         for i, blk in enumerate(self.attn_blocks):
+            b = local if self.config.layer_window(i) is not None else bounds
             if i < n_ckpt:
-                x, res = checkpoint(blk, x, res, rope, x_bias, True, bounds, use_reentrant=False)
+                x, res = checkpoint(blk, x, res, rope, x_bias, True, b, use_reentrant=False)
             else:
-                x, res = blk(x, res, rope, x_bias, True, bounds)
+                x, res = blk(x, res, rope, x_bias, True, b)
             x_bias = blk.fused_out_bias(x)
         h, _ = self.layer_norm(x, res, x_bias=x_bias)
         return h
@@ -511,7 +534,8 @@ class GPT(nn.Module):
                 doc_mask: Optional[bool] = None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
         """Under tensor/sequence/context parallelism the loss is the mean over THIS rank's tokens
         (SP / CP: its sequence shard); the Trainer scales the gradients accordingly.
-        ``doc_mask``: None follows ``config.doc_mask``; False runs the window as one document (generation)."""
+        ``doc_mask``: None follows ``config.doc_mask``; False runs the window as one document (generation).
+        A sliding window (``config.sliding_window``) is architecture and applies either way."""
         idx, targets = self._shard_inputs(idx, targets)
         h = self._trunk(idx, doc_mask)
         pg = self.parallel
@@ -536,9 +560,12 @@ class GPT(nn.Module):
         x = self._embed(idx)
         rope = self.rope_tables(idx.device, idx.shape[1])
         res = None
-        for blk in self.attn_blocks[:-1]:
-            x, res = blk(x, res, rope)
-        return self.attn_blocks[-1].forward_embedding(x, res, rope)
+        W, (B, T) = self.config.sliding_window, idx.shape
+        local = ops.window_bounds(B, T, W, idx.device) if W is not None and W < T else None
+        bounds = [local if self.config.layer_window(i) is not None else None for i in range(len(self.attn_blocks))]
+        for blk, b in zip(self.attn_blocks[:-1], bounds):
+            x, res = blk(x, res, rope, bounds=b)
+        return self.attn_blocks[-1].forward_embedding(x, res, rope, bounds[-1])
 
     # ------------------------------------------------------------------
     @torch.no_grad()

@@ -694,6 +694,24 @@ def bounds_from_start(kv_start):
     return (torch.searchsorted(kv_start.contiguous(), j, right=True) - 1).to(torch.int32)
 
 
+def window_bounds(B: int, T: int, window: int, device, doc=None):
+    """Per-row key bounds (kv_start, q_last), int32 [B, T] each, of a sliding window of ``window`` keys (the query
+    included): kv_start[i] = max(0, i - window + 1), q_last[j] = min(T - 1, j + window - 1).  With ``doc`` (the
+    bounds of ``doc_bounds``) the intersection of window and document: kv_start = max(doc_start, i - window + 1),
+    q_last = min(doc_q_last, j + window - 1).  Closed form in fixed-shape device ops, so it can sit inside a
+    captured step; nothing is kept between calls."""
+    if window < 1:
+        raise ValueError(f"window_bounds: window={window} must be >= 1")
+    w = min(int(window), T) - 1
+    pos = torch.arange(T, device=device, dtype=torch.int32).expand(B, T)
+    kv_start = (pos - w).clamp_min(0)
+    q_last = (pos + w).clamp_max(T - 1)
+    if doc is not None:
+        kv_start = torch.maximum(kv_start, doc[0].to(torch.int32))
+        q_last = torch.minimum(q_last, doc[1].to(torch.int32))
+    return kv_start.contiguous(), q_last.contiguous()
+
+
 def _bounds_mask(kv_start):
     """Boolean visibility [B, 1, T, T] of the bounds (query i, key j): kv_start[b, i] <= j <= i."""
     T = kv_start.shape[1]
@@ -1012,12 +1030,23 @@ def attention_packed(qkv, n_head: int, n_kv_head: int, causal: bool = True, scal
     return o.reshape(B, T, n_head * D)
 
 
-def attention(q, k, v, causal: bool = True, scale: Optional[float] = None, return_lse: bool = False):
+def attention(q, k, v, causal: bool = True, scale: Optional[float] = None, return_lse: bool = False,
+              kv_start: Optional[torch.Tensor] = None):
     """Unpacked attention q [B,T,H,D], k/v [B,S,Hkv,D] (forward only; used by the
     KV-cache decode and context-parallel paths).  Queries are aligned to the end
-    of the key sequence."""
+    of the key sequence.  ``kv_start`` (int32 [B, T], see ``window_bounds``; needs ``causal`` and S == T, a
+    prefill from position 0): query i sees keys kv_start[b, i] <= j <= i only."""
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if kv_start is not None:
+        if not causal or k.shape[1] != q.shape[1]:
+            raise ValueError(f"attention: kv_start needs causal attention over as many keys as queries "
+                             f"(causal={causal}, T={q.shape[1]}, S={k.shape[1]})")
+        if _hip(q):
+            o, lse = _ops().attn_fwd(q, k, v, causal, scale, kv_start)
+        else:
+            o, lse = ref.attention(q, k, v, causal=True, scale=scale, bounds=(kv_start, None))
+        return (o, lse) if return_lse else o
     if _hip(q) and q.shape[1] == 1 and not return_lse and q.shape[2] // k.shape[2] in (1, 2, 4, 8):
         # one query per sequence (KV-cache decode): split-KV streaming kernel (csrc/attn_decode.hip)
         return _ops().attn_decode(q, k, v, scale)
@@ -1028,20 +1057,25 @@ def attention(q, k, v, causal: bool = True, scale: Optional[float] = None, retur
     return (o, lse) if return_lse else o
 
 
-def attention_decode(q, k, v, seqlen: Optional[torch.Tensor] = None, scale: Optional[float] = None):
+def attention_decode(q, k, v, seqlen: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                     window: Optional[int] = None):
     """Single-query attention q [B,1,H,D] over cached k/v [B,S,Hkv,D]; ``seqlen`` (int32 [1]
     device tensor) optionally limits the keys to the first ``seqlen`` rows, read on the
-    device so a captured decode step (hipGraph) replays at every position."""
+    device so a captured decode step (hipGraph) replays at every position.  ``window`` (sliding-window
+    attention, a host constant): only the last ``window`` of those keys, [max(0, n - window), n), are seen."""
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if window is not None and window < 1:
+        raise ValueError(f"attention_decode: window={window} must be >= 1 (None: no window)")
     if _hip(q):
-        return _ops().attn_decode(q, k, v, scale, seqlen)
+        return _ops().attn_decode(q, k, v, scale, seqlen, int(window or 0))
+    W = window if window is not None else k.shape[1]
     if seqlen is not None and seqlen.numel() > 1:  # one key count per sequence
-        return torch.cat([ref.attention(q[b:b + 1], k[b:b + 1, :int(n)], v[b:b + 1, :int(n)], causal=False,
+        return torch.cat([ref.attention(q[b:b + 1], k[b:b + 1, max(0, int(n) - W):int(n)],
+                                        v[b:b + 1, max(0, int(n) - W):int(n)], causal=False,
                                         scale=scale)[0] for b, n in enumerate(seqlen.tolist())])
-    if seqlen is not None:
-        n = int(seqlen.item())
-        k, v = k[:, :n], v[:, :n]
+    n = int(seqlen.item()) if seqlen is not None else k.shape[1]
+    k, v = k[:, max(0, n - W):n], v[:, max(0, n - W):n]
     o, _ = ref.attention(q, k, v, causal=False, scale=scale)
     return o
 

@@ -179,7 +179,7 @@ def register() -> None:
         return [q.new_empty(q.shape), q.new_empty((B, H, T), dtype=f32)]
 
     @_reg("attn_decode")
-    def _(q, k, v, scale, seqlen=None):
+    def _(q, k, v, scale, seqlen=None, window=0):
         return q.new_empty(q.shape)
 
     @_reg("attn_bwd")

@@ -309,6 +309,8 @@ def parallelize_gpt(model, pg: ParallelGroups):
     if cfg.doc_mask and (pg.tp > 1 or pg.cp > 1):
         # the sharded attention paths (TPAttention, ring / Ulysses) take no per-row key bounds
         raise ValueError(f"doc_mask is not supported with tensor or context parallelism (tp={pg.tp}, cp={pg.cp})")
+    if cfg.sliding_window is not None and (pg.tp > 1 or pg.cp > 1):
+        raise ValueError(f"sliding_window is not supported with tensor or context parallelism (tp={pg.tp}, cp={pg.cp})")
     if cfg.qk_norm and (pg.tp > 1 or pg.cp > 1):
         # TP: the replicated gains see only the local heads, so their gradients would need a TP-group sum
         # (sync_replicated_grads covers sequence parallelism only); CP: ring / Ulysses attention take their own path

@@ -44,7 +44,7 @@ def model_config_from(cfg: dict) -> ModelConfig:
     preset = cfg.get("model_preset")
     dims = {k: cfg[k] for k in ("vocab_size", "context_length", "n_embed", "n_head", "n_blocks") if k in cfg}
     extra = {k: cfg[k] for k in ("n_kv_head", "ffn_hidden", "activation_checkpointing", "qk_norm", "qk_norm_eps",
-                                  "doc_mask", "doc_sep_token")
+                                  "doc_mask", "doc_sep_token", "sliding_window", "sliding_window_pattern")
              if cfg.get(k) is not None}
     if preset:
         mc = get_preset(preset)
@@ -59,6 +59,10 @@ def check_parallel_config(cfg: dict) -> None:
     tp, cp = int(cfg.get("tp_size", 1)), int(cfg.get("cp_size", 1))
     if (tp > 1 or cp > 1) and model_config_from(cfg).doc_mask:
         raise ValueError(f"doc_mask is not supported with tensor or context parallelism (tp_size={tp}, "
+                         f"cp_size={cp}): the sharded attention paths (sequence-parallel, ring, Ulysses) take no "
+                         "per-row key bounds")
+    if (tp > 1 or cp > 1) and model_config_from(cfg).sliding_window is not None:
+        raise ValueError(f"sliding_window is not supported with tensor or context parallelism (tp_size={tp}, "
                          f"cp_size={cp}): the sharded attention paths (sequence-parallel, ring, Ulysses) take no "
                          "per-row key bounds")
     if (tp > 1 or cp > 1) and model_config_from(cfg).qk_norm:
