@@ -21,6 +21,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
+from ..ab import ab as _ab
 from . import _lib
 from . import reference as ref
 
@@ -78,7 +79,11 @@ def _ops():
 # read-add-write epilogues) instead of returning a fresh tensor that autograd's
 # AccumulateGrad would then add in a separate pass.  ``_notify`` tells the
 # data-parallel engine that a contribution landed (it replaces the
-# post-accumulate-grad hook for these).
+# post-accumulate-grad hook for these).  The engines count the notifications
+# of each parameter, so a writer takes its slot, writes it and notifies if and
+# only if it wrote, else returns a fresh tensor: ``_linear_param_grads``,
+# ``_bias_param_grad`` and ``_bias_grad_by`` below are that sequence for the
+# linear layers' weights and biases.
 # ---------------------------------------------------------------------------
 def _acc_target(p):
     """The flat-gradient slot a writer ADDS into.  A slot the optimizer left uncleared (lazy zeroing,
@@ -112,6 +117,62 @@ def _notify(p):
         cb()
 
 
+def _linear_param_grads(dy2, x2, w, b, need_w: bool = True, need_b: bool = True, fuse_bias: bool = True):
+    """(dw, db) of y = x W^T + b from dy2 [rows, N] and x2 [rows, K]: each goes into its parameter's flat-gradient
+    slot (None is returned for it and the parameter is notified, weight before bias) or comes back as a fresh
+    tensor.  The weight-gradient GEMM writes the whole of dW (``_set_target``); with ``fuse_bias`` the bias
+    gradient rides along it when both have slots (FUSED_WGRAD_BIAS), else it is a ``bias_grad`` pass of its own."""
+    dw = db = None
+    need_b = need_b and b is not None
+    if need_w:
+        tgt, fresh = _set_target(w)
+        # (no weight slot: no fused bias target either, the bias takes the separate pass below)
+        btgt = _acc_target(b) if need_b and fuse_bias and tgt is not None and FUSED_WGRAD_BIAS else None
+        dw = _weight_grad(dy2, x2, tgt, btgt, overwrite=fresh)
+        if tgt is not None:
+            _notify(w)
+        if btgt is not None:
+            _notify(b)
+            need_b = False
+    if need_b:
+        db = _bias_param_grad(dy2, b)
+    return dw, db
+
+
+def _bias_param_grad(dy2, b):
+    """Column sums of dy2 added into ``b``'s flat-gradient slot (-> None, ``b`` notified), else returned."""
+    tgt = _acc_target(b)
+    if tgt is None:
+        return _ops().bias_grad(dy2.contiguous())
+    _ops().bias_grad(dy2.contiguous(), tgt)
+    _notify(b)
+    return None
+
+
+def _bias_grad_by(b, run):
+    """(run(acc), db) for a kernel ``run`` that adds ``b``'s gradient into ``acc`` beside its own work (a GEMM
+    epilogue's column sums): ``acc`` is b's flat-gradient slot (db None, ``b`` notified) or fresh fp32 zeros."""
+    tgt = _acc_target(b)
+    acc = tgt if tgt is not None else torch.zeros(b.shape[0], device=b.device, dtype=torch.float32)
+    out = run(acc)
+    if tgt is None:
+        return out, acc.to(b.dtype)
+    _notify(b)
+    return out, None
+
+
+def _bias_ext(flag, b) -> bool:
+    """A bias gradient is left to the consumer's backward kernel (the next norm's dx column sums, the activation
+    backward) only while that consumer runs on the HIP kernels."""
+    return bool(flag and b is not None and not (_TORCH_OPS & {"norm", "act"}))
+
+
+def _gemm_lt(x2, w, b, epilogue: int = 0, res2=None):
+    """x2 W^T + b (+ res2, added by the GEMM: one rounding) on hipBLASLt with epilogue 0 none / 2 ReLU; contiguous
+    2-D operands.  Deterministic mode pins the first candidate instead of timing them."""
+    return _ops().gemm_lt(x2, w, b, epilogue, not torch.are_deterministic_algorithms_enabled(), res2)[0]
+
+
 class _LinearFn(torch.autograd.Function):
     """y = x W^T + b on hipBLASLt; backward accumulates dW (beta=1 GEMM) and db in place.
 
@@ -128,53 +189,25 @@ class _LinearFn(torch.autograd.Function):
         if res is not None:  # + the residual stream, added by the GEMM (resid_gemm_ok)
             N = weight.shape[0]
             # (gemm_lt takes contiguous operands only; reshape of a strided view can stay strided)
-            return _ops().gemm_lt(x.reshape(-1, x.shape[-1]).contiguous(), weight, bias, 0,
-                                  not torch.are_deterministic_algorithms_enabled(),
-                                  res.reshape(-1, N))[0].view(*x.shape[:-1], N)
+            return _gemm_lt(x.reshape(-1, x.shape[-1]).contiguous(), weight, bias, 0,
+                            res.reshape(-1, N)).view(*x.shape[:-1], N)
         return F.linear(x, weight, bias)
 
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = _dgrad(dy, weight)
-        dy2 = dy.reshape(-1, dy.shape[-1])
-        # the bias gradient rides along the weight-gradient GEMM when both go into flat targets
-        btgt = None
-        if (ctx.b is not None and ctx.needs_input_grad[2] and not ctx.bias_ext and ctx.needs_input_grad[1]
-                and FUSED_WGRAD_BIAS):
-            btgt = _acc_target(ctx.b)
-        if ctx.needs_input_grad[1]:
-            x2 = x.reshape(-1, x.shape[-1])
-            tgt, fresh = _set_target(ctx.w)
-            if tgt is None:
-                btgt = None
-            dw = _weight_grad(dy2, x2, tgt, btgt, overwrite=fresh)
-            if tgt is not None:
-                _notify(ctx.w)
-        if btgt is not None:
-            _notify(ctx.b)
-        elif ctx.b is not None and ctx.needs_input_grad[2] and not ctx.bias_ext:
-            tgt = _acc_target(ctx.b)
-            if tgt is not None:
-                _ops().bias_grad(dy2.contiguous(), tgt)
-                _notify(ctx.b)
-            else:
-                db = _ops().bias_grad(dy2.contiguous())
+        dx = _dgrad(dy, weight) if ctx.needs_input_grad[0] else None
+        dw, db = _linear_param_grads(dy.reshape(-1, dy.shape[-1]), x.reshape(-1, x.shape[-1]), ctx.w, ctx.b,
+                                     ctx.needs_input_grad[1], ctx.needs_input_grad[2] and not ctx.bias_ext)
         ctx.w = ctx.b = None
         return dx, dw, db, None, (dy if ctx.has_res else None)
 
-
-import os as _os
-
-from ..ab import ab as _ab
 
 # weight-gradient GEMM engine: "hip" = hand-written split-K MFMA kernel (csrc/gemm_wgrad.hip),
 # default: 824-1114 TFLOP/s at M=65536 vs 432-1003 for hipBLASLt's token-major "NT" kernels
 # (bench/gemm_bench.py, profiles/r1_wgrad_v2_gemm_bench.jsonl); "blas" = hipBLASLt/rocBLAS
 # through torch (beta=1 addmm into the flat gradient)
-WGRAD_ENGINE = _os.environ.get("PLLM_WGRAD", "hip")
+WGRAD_ENGINE = os.environ.get("PLLM_WGRAD", "hip")
 # (tokens M, P, Q) weight-gradient shapes where hipBLASLt measured faster than the hand-written
 # kernel on MI355X (bench/gemm_bench.py --shapes llama --M 16384, profiles/r1_wgrad_plan_ab.jsonl):
 # llama-1.3B at 8 x 2048 tokens -- QKV, MLP down projection and LM head
@@ -189,15 +222,26 @@ WGRAD_BLAS_SHAPES = {(16384, 6144, 2048), (16384, 2048, 5504), (16384, 50304, 20
 FUSED_WGRAD_BIAS = _ab("wgrad_bias", True)
 
 
+def _shadow(w):
+    """The transposed shadow W^T the optimizer keeps of ``w`` (FlatAdamW ``transposed_shadow``), or None without
+    one or when ``w`` changed since its last refresh."""
+    wt = getattr(w, "_pllm_wT", None)
+    return wt if wt is not None and getattr(w, "_pllm_wT_ver", None) == w._version else None
+
+
+def _shadow_or_t(w):
+    """W^T contiguous: the shadow when it is current, else a transposed copy."""
+    wt = _shadow(w)
+    return wt if wt is not None else w.t().contiguous()
+
+
 def _dgrad(dy, weight):
     """dx = dy @ weight.  When the optimizer keeps a transposed shadow of the weight
     (FlatAdamW ``transposed_shadow``), the product runs as dy @ (W^T)^T: hipBLASLt's
     kernels for that operand layout are 10-15% faster at these shapes than for
     dy @ W (bench/gemm_fwd_bench.py: dgrad_nt vs dgrad_nn)."""
-    wt = getattr(weight, "_pllm_wT", None)
-    if wt is not None and getattr(weight, "_pllm_wT_ver", None) == weight._version:
-        return dy @ wt.t()
-    return dy @ weight
+    wt = _shadow(weight)
+    return dy @ (wt.t() if wt is not None else weight)
 
 
 def _weight_grad(dy2, x2, tgt, btgt=None, overwrite: bool = False):
@@ -234,20 +278,15 @@ def _weight_grad(dy2, x2, tgt, btgt=None, overwrite: bool = False):
 def linear(x, weight, bias=None, bias_grad_external: bool = False, residual=None):
     """``residual`` (only when resid_gemm_ok holds -- the caller checks): x W^T + b + residual."""
     if _hip_op("linear", x) and torch.is_grad_enabled() and weight.requires_grad:
-        # a bias gradient is left to the consumer's kernel only while that consumer (norm / act)
-        # runs on the HIP kernels
-        ext = bias_grad_external and bias is not None and not (_TORCH_OPS & {"norm", "act"})
-        return _LinearFn.apply(x, weight, bias, ext, residual)
+        return _LinearFn.apply(x, weight, bias, _bias_ext(bias_grad_external, bias), residual)
     if residual is not None:
         return F.linear(x, weight, bias) + residual
-    if _hip(x) and not (torch.is_grad_enabled() and x.requires_grad):
-        # decode-sized inference projections (<= 8 token rows): weight-streaming skinny GEMM
-        # (csrc/gemv.hip) instead of the training-sized library tiles
-        K = x.shape[-1]
-        rows = x.numel() // K if K else 0
-        if 0 < rows <= 8 and K % 8 == 0 and weight.is_contiguous() and _aligned16(weight):
-            y = _ops().gemv(x.reshape(rows, K).contiguous(), weight, bias)[0]
-            return y.view(*x.shape[:-1], weight.shape[0])
+    # decode-sized inference projections: weight-streaming skinny GEMM (csrc/gemv.hip) instead of the
+    # training-sized library tiles.  (Grad mode alone does not rule it out here as it does in _gemv_ok: a
+    # frozen weight under an input that needs no gradient is still inference.)
+    if not (torch.is_grad_enabled() and x.requires_grad) and _gemv_shape_ok(x, weight):
+        y = _ops().gemv(x.reshape(-1, x.shape[-1]).contiguous(), weight, bias)[0]
+        return y.view(*x.shape[:-1], weight.shape[0])
     return F.linear(x, weight, bias)
 
 
@@ -273,7 +312,7 @@ def gemm_config(reserve_cus: Optional[int] = None, persistent: Optional[bool] = 
 # the fused data-gradient epilogue (act' + b1's gradient: 476-480 vs 512 us per GPT-2 layer, measured in
 # round 3); "all" = the forward activation in the GEMM epilogue too (its main loop is
 # still slower than hipBLASLt's: 423-440 vs 408 us with the separate GELU pass); "0" = neither
-_FM = _os.environ.get("PLLM_FUSED_MLP", "bwd")
+_FM = os.environ.get("PLLM_FUSED_MLP", "bwd")
 FUSED_MLP = _FM in ("1", "all", "bwd")
 FUSED_MLP_FWD = _FM in ("1", "all")
 # PLLM_AB fused_swiglu_fwd=1|0: the llama up-projection with its SwiGLU in the GEMM epilogue (epilogue 7)
@@ -318,7 +357,7 @@ class _FusedMLPFn(torch.autograd.Function):
             # ReLU in hipBLASLt's own bias epilogue: one pass writes the activation (the
             # backward needs only its sign); relu commutes with the bf16 rounding, so the result
             # equals the separate pass
-            a = _ops().gemm_lt(x2.contiguous(), w1, b1, 2, not torch.are_deterministic_algorithms_enabled())[0]
+            a = _gemm_lt(x2.contiguous(), w1, b1, 2)
             ctx.save_for_backward(x2, a)
         elif not FUSED_MLP_FWD:
             pre = F.linear(x2, w1, b1)
@@ -338,8 +377,7 @@ class _FusedMLPFn(torch.autograd.Function):
         ctx.xshape = x.shape
         ctx.has_res = res is not None
         if res is not None:  # the block's residual stream added in the GEMM (one rounding, see resid_gemm_ok)
-            return _ops().gemm_lt(a, w2, b2, 0, not torch.are_deterministic_algorithms_enabled(),
-                                  res.reshape(-1, C))[0].view(*x.shape[:-1], C)
+            return _gemm_lt(a, w2, b2, 0, res.reshape(-1, C)).view(*x.shape[:-1], C)
         return F.linear(a, w2, b2).view(*x.shape[:-1], C)
 
     @staticmethod
@@ -352,36 +390,16 @@ class _FusedMLPFn(torch.autograd.Function):
         w1, b1, w2, b2 = ctx.params
         ctx.params = None
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
-        dw1 = db1 = dw2 = db2 = None
-        # down projection: weight and bias gradients
-        tgt, fresh = _set_target(w2)
-        dw2 = _weight_grad(dy2, a, tgt, overwrite=fresh)
-        if tgt is not None:
-            _notify(w2)
-        if b2 is not None and not ctx.ext:
-            tgt = _acc_target(b2)
-            if tgt is not None:
-                _ops().bias_grad(dy2, tgt)
-                _notify(b2)
-            else:
-                db2 = _ops().bias_grad(dy2)
-        # its data gradient fused with the activation backward and b1's gradient
-        w2t = getattr(w2, "_pllm_wT", None)
-        if w2t is None or getattr(w2, "_pllm_wT_ver", None) != w2._version:
-            w2t = w2.t().contiguous()
-        tgt = _acc_target(b1)
-        bacc = tgt if tgt is not None else torch.zeros(b1.shape[0], device=dy2.device, dtype=torch.float32)
-        dpre = _ops().gemm_tn(dy2, w2t, None, 3 if ctx.gelu else 4, pre, bacc)[0]
-        if tgt is not None:
-            _notify(b1)
-        else:
-            db1 = bacc.to(b1.dtype)
+        # down projection: weight and bias gradients.  Two differences from _LinearFn, both kept: the weight
+        # gradients are formed whatever needs_input_grad says, and b2's gradient is always a bias_grad pass of
+        # its own (fused into the weight-gradient GEMM another kernel would form the sum: other bits)
+        dw2, db2 = _linear_param_grads(dy2, a, w2, b2, need_b=not ctx.ext, fuse_bias=False)
+        # its data gradient fused with the activation backward and b1's gradient (the epilogue's column sums)
+        w2t = _shadow_or_t(w2)
+        dpre, db1 = _bias_grad_by(b1, lambda acc: _ops().gemm_tn(dy2, w2t, None, 3 if ctx.gelu else 4, pre, acc)[0])
         # up projection
         dx = _dgrad(dpre, w1) if ctx.needs_input_grad[0] else None
-        tgt, fresh = _set_target(w1)
-        dw1 = _weight_grad(dpre, x2, tgt, overwrite=fresh)
-        if tgt is not None:
-            _notify(w1)
+        dw1, _ = _linear_param_grads(dpre, x2, w1, None)
         if dx is not None:
             dx = dx.view(ctx.xshape)
         return dx, dw1, db1, dw2, db2, None, None, (dy if ctx.has_res else None)
@@ -389,8 +407,7 @@ class _FusedMLPFn(torch.autograd.Function):
 
 def fused_mlp(x, w1, b1, w2, b2, act: str, out_bias_ext: bool = False, residual=None):
     """``residual``: y + residual is returned (added by the down projection's GEMM, resid_gemm_ok)."""
-    ext = bool(out_bias_ext and b2 is not None and not (_TORCH_OPS & {"norm", "act"}))
-    return _FusedMLPFn.apply(x, w1, b1, w2, b2, act == "gelu", ext, residual)
+    return _FusedMLPFn.apply(x, w1, b1, w2, b2, act == "gelu", _bias_ext(out_bias_ext, b2), residual)
 
 
 # PLLM_AB resid_gemm=1|0: a block's residual add (reference: x = x + attn(ln1(x)); x = x + mlp(ln2(x)),
@@ -462,19 +479,11 @@ class _FusedSwiGLUMLPFn(torch.autograd.Function):
         w1, w2 = ctx.params
         ctx.params = None
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
-        tgt, fresh = _set_target(w2)
-        dw2 = _weight_grad(dy2, a, tgt, overwrite=fresh)
-        if tgt is not None:
-            _notify(w2)
-        w2t = getattr(w2, "_pllm_wT", None)
-        if w2t is None or getattr(w2, "_pllm_wT_ver", None) != w2._version:
-            w2t = w2.t().contiguous()
-        dgu = _ops().gemm_tn(dy2, w2t, None, 5, gu, None)[0]
+        # (both weight gradients whatever needs_input_grad says, as in _FusedMLPFn)
+        dw2, _ = _linear_param_grads(dy2, a, w2, None)
+        dgu = _ops().gemm_tn(dy2, _shadow_or_t(w2), None, 5, gu, None)[0]
         dx = _dgrad(dgu, w1) if ctx.needs_input_grad[0] else None
-        tgt, fresh = _set_target(w1)
-        dw1 = _weight_grad(dgu, x2, tgt, overwrite=fresh)
-        if tgt is not None:
-            _notify(w1)
+        dw1, _ = _linear_param_grads(dgu, x2, w1, None)
         if dx is not None:
             dx = dx.view(ctx.xshape)
         return dx, dw1, dw2
@@ -493,11 +502,16 @@ def _aligned16(t) -> bool:
     return (t.storage_offset() * t.element_size()) % 16 == 0
 
 
-def _gemv_ok(x, weight):
+def _gemv_shape_ok(x, weight) -> bool:
+    """Decode-sized input (<= 8 token rows) on the HIP path whose weight the skinny GEMM (csrc/gemv.hip) takes."""
     K = x.shape[-1]
     rows = x.numel() // K if K else 0
-    return (_hip(x) and not torch.is_grad_enabled() and 0 < rows <= 8 and K % 8 == 0
-            and weight.is_contiguous() and _aligned16(weight))
+    return _hip(x) and 0 < rows <= 8 and K % 8 == 0 and weight.is_contiguous() and _aligned16(weight)
+
+
+def _gemv_ok(x, weight):
+    # (the fused norm + GEMM of norm_linear has no backward at all: never under grad mode, see linear())
+    return not torch.is_grad_enabled() and _gemv_shape_ok(x, weight)
 
 
 def norm_linear(x, residual, norm_weight, norm_bias, eps: float, rms: bool, weight, bias=None,
@@ -583,8 +597,8 @@ class _NormFn(torch.autograd.Function):
         ds2 = ds.reshape(-1, C).contiguous() if ds is not None else None
         tw = _acc_target(ctx.w)
         tb = _acc_target(ctx.b) if ctx.has_bias else None
-        txb = _acc_target(ctx.xb) if ctx.xb is not None else None
         direct = tw is not None and (not ctx.has_bias or tb is not None)
+        txb = _acc_target(ctx.xb) if direct else None  # x_bias rides in the kernel only on its accumulating form
         dxb = None
         if direct:
             outs = (_ops().norm_bwd_acc(dy2, s, weight, mean, rstd, ds2, ctx.has_bias, ctx.rms, tw, tb, txb),)
@@ -598,11 +612,8 @@ class _NormFn(torch.autograd.Function):
             outs = _ops().norm_bwd(dy2, s, weight, mean, rstd, ds2, ctx.has_bias, ctx.rms)
             dw = outs[1]
             db = outs[2] if ctx.has_bias else None
-            if txb is not None:
-                _ops().bias_grad(outs[0], txb)
-                _notify(ctx.xb)
-        if ctx.xb is not None and txb is None:
-            dxb = _ops().bias_grad(outs[0])
+        if ctx.xb is not None and txb is None:  # the column sums of dx as a pass of their own
+            dxb = _bias_param_grad(outs[0], ctx.xb)
         ctx.w = ctx.b = ctx.xb = None
         dx = outs[0].view(ctx.shp)
         return dx, (dx if ctx.has_res else None), dw, db, None, None, dxb
@@ -816,8 +827,7 @@ class _AttnProjFn(torch.autograd.Function):
         ctx.has_res = res is not None
         if res is not None:  # the block's residual stream added in the GEMM (resid_gemm_ok)
             C = w.shape[0]
-            return _ops().gemm_lt(o.view(B * T, H * D), w, b, 0, not torch.are_deterministic_algorithms_enabled(),
-                                  res.reshape(-1, C))[0].view(B, T, C)
+            return _gemm_lt(o.view(B * T, H * D), w, b, 0, res.reshape(-1, C)).view(B, T, C)
         return F.linear(o.view(B, T, H * D), w, b)
 
     @staticmethod
@@ -830,29 +840,10 @@ class _AttnProjFn(torch.autograd.Function):
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
         o2 = o.view(B * T, H * D)
         # projection weight / bias gradients (as _LinearFn.backward)
-        dw = db = None
-        need_b = b is not None and ctx.needs_input_grad[8] and not ctx.bias_ext
-        if ctx.needs_input_grad[7]:
-            tgt, fresh = _set_target(w)
-            btgt = _acc_target(b) if (need_b and tgt is not None and FUSED_WGRAD_BIAS) else None
-            dw = _weight_grad(dy2, o2, tgt, btgt, overwrite=fresh)
-            if tgt is not None:
-                _notify(w)
-            if btgt is not None:
-                _notify(b)
-                need_b = False
-        if need_b:
-            bt = _acc_target(b)
-            if bt is not None:
-                _ops().bias_grad(dy2, bt)
-                _notify(b)
-            else:
-                db = _ops().bias_grad(dy2)
+        dw, db = _linear_param_grads(dy2, o2, w, b, ctx.needs_input_grad[7],
+                                     ctx.needs_input_grad[8] and not ctx.bias_ext)
         # dO and delta from one GEMM through W_o's transposed shadow
-        wt = getattr(w, "_pllm_wT", None)
-        if wt is None or getattr(w, "_pllm_wT_ver", None) != w._version:
-            wt = w.t().contiguous()
-        do2, delta = _ops().gemm_tn(dy2, wt, None, 6, o2, None, T)
+        do2, delta = _ops().gemm_tn(dy2, _shadow_or_t(w), None, 6, o2, None, T)
         dqkv, dwq, dwk = _attn_packed_bwd(do2.view(B, T, H, D), qkv, qk, o, lse, ctx.cfg, cos, sin, delta,
                                           qkn=qkn, rstd=rstd, kv_start=kv_start, q_last=q_last)
         return (dqkv, None, None, None, None, None, None, dw, db, None, (dy if ctx.has_res else None), dwq, dwk,
@@ -885,13 +876,14 @@ def attention_proj(qkv, n_head: int, n_kv_head: int, w, b, causal: bool = True, 
     backward (see _AttnProjFn).  ``bounds``: see attention_packed."""
     D = qkv.shape[-1] // (n_head + 2 * n_kv_head)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
-    ext = bool(bias_grad_external and b is not None and not (_TORCH_OPS & {"norm", "act"}))
     kv_start, q_last = bounds if bounds is not None else (None, None)
     if q_norm_weight is None:
-        return _AttnProjFn.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin, w, b, ext, residual,
-                                 None, None, qk_norm_eps, kv_start, q_last)
-    return _AttnProjFn.apply(qkv.contiguous(), n_head, n_kv_head, causal, scale, rope_cos, rope_sin, w, b, ext,
-                             residual, q_norm_weight, k_norm_weight, qk_norm_eps, kv_start, q_last)
+        k_norm_weight = None
+    else:  # the QK-norm pre- and post-pass take the packed tensor contiguous
+        qkv = qkv.contiguous()
+    return _AttnProjFn.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin, w, b,
+                             _bias_ext(bias_grad_external, b), residual, q_norm_weight, k_norm_weight, qk_norm_eps,
+                             kv_start, q_last)
 
 
 _ATTN_WS_MB = [None]
@@ -1004,10 +996,10 @@ def attention_packed(qkv, n_head: int, n_kv_head: int, causal: bool = True, scal
     if _hip_op("attn", qkv):
         # RoPE: one rope_qk pre-pass rotates q / k, the backward kernels rotate dq / dk back
         if q_norm_weight is None:
-            return _FlashAttnPacked.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin,
-                                          None, None, qk_norm_eps, kv_start, q_last)
-        # QK-norm: qk_norm_rope is that pre-pass, qk_norm_bwd_ a post-pass over dqkv
-        return _FlashAttnPacked.apply(qkv.contiguous(), n_head, n_kv_head, causal, scale, rope_cos, rope_sin,
+            k_norm_weight = None
+        else:  # QK-norm: qk_norm_rope is that pre-pass, qk_norm_bwd_ a post-pass over dqkv, both on contiguous qkv
+            qkv = qkv.contiguous()
+        return _FlashAttnPacked.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin,
                                       q_norm_weight, k_norm_weight, qk_norm_eps, kv_start, q_last)
     if q_norm_weight is not None:
         q, k = qk_norm_packed(qkv, q_norm_weight, k_norm_weight, qk_norm_eps, n_head, n_kv_head, rope_cos, rope_sin)
@@ -1097,56 +1089,31 @@ def attention_block_bwd(do, q, k, v, o, lse, causal: bool = True, scale: Optiona
 # ---------------------------------------------------------------------------
 # activations (op ids of the HIP act kernels: 0 relu, 1 gelu-tanh)
 # ---------------------------------------------------------------------------
-class _GeluFn(torch.autograd.Function):
-    """GELU(tanh); with ``bias`` (the producing linear's bias, created with
-    bias_grad_external=True) the backward kernel also emits that bias's gradient."""
+class _ActFn(torch.autograd.Function):
+    """GELU(tanh) (``kind`` 1) / ReLU (0, the reference MLP's activation); with ``bias`` (the producing linear's
+    bias, created with bias_grad_external=True) the backward kernel also emits that bias's gradient."""
 
     @staticmethod
-    def forward(ctx, x, bias):
-        ctx.save_for_backward(x)
-        ctx.b = bias
-        return _ops().act_fwd(x, 1)
-
-    @staticmethod
-    def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
-        dy = dy.contiguous()
-        b, ctx.b = ctx.b, None
-        if b is None:
-            return _ops().act_bwd(dy, x, 1), None
-        tgt = _acc_target(b)
-        if tgt is not None:
-            dx = _ops().act_bwd_bias(dy, x, 1, tgt)
-            _notify(b)
-            return dx, None
-        dx = _ops().act_bwd(dy, x, 1)
-        return dx, _ops().bias_grad(dx)
-
-
-class _ReluFn(torch.autograd.Function):
-    """ReLU (reference MLP activation); optional fused bias gradient like _GeluFn."""
-
-    @staticmethod
-    def forward(ctx, x, bias):
-        y = _ops().act_fwd(x, 0)
-        ctx.save_for_backward(y)
-        ctx.b = bias
+    def forward(ctx, x, bias, kind):
+        y = _ops().act_fwd(x, kind)
+        ctx.save_for_backward(x if kind == 1 else y)  # GELU's derivative needs its input, ReLU's only the sign of y
+        ctx.b, ctx.kind = bias, kind
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        (y,) = ctx.saved_tensors
+        (t,) = ctx.saved_tensors
         dy = dy.contiguous()
         b, ctx.b = ctx.b, None
         if b is None:
-            return _ops().act_bwd(dy, y, 0), None
-        tgt = _acc_target(b)
+            return _ops().act_bwd(dy, t, ctx.kind), None, None
+        tgt = _acc_target(b)  # (not _bias_grad_by: without a slot it is another kernel pair, not fresh zeros)
         if tgt is not None:
-            dx = _ops().act_bwd_bias(dy, y, 0, tgt)
+            dx = _ops().act_bwd_bias(dy, t, ctx.kind, tgt)
             _notify(b)
-            return dx, None
-        dx = _ops().act_bwd(dy, y, 0)
-        return dx, _ops().bias_grad(dx)
+            return dx, None, None
+        dx = _ops().act_bwd(dy, t, ctx.kind)
+        return dx, _ops().bias_grad(dx), None
 
 
 class _SwigluFn(torch.autograd.Function):
@@ -1163,7 +1130,7 @@ class _SwigluFn(torch.autograd.Function):
 
 def gelu(x, bias: Optional[torch.Tensor] = None):
     if _hip_op("act", x):
-        return _GeluFn.apply(x.contiguous(), bias)
+        return _ActFn.apply(x.contiguous(), bias, 1)
     if _stock("act"):
         return F.gelu(x, approximate="tanh")
     return ref.gelu_tanh(x)
@@ -1177,7 +1144,7 @@ def swiglu(gate_up):
 
 def relu(x, bias: Optional[torch.Tensor] = None):
     if _hip_op("act", x):
-        return _ReluFn.apply(x.contiguous(), bias)
+        return _ActFn.apply(x.contiguous(), bias, 0)
     return ref.relu(x)
 
 
@@ -1242,7 +1209,7 @@ def embedding(idx, wte, wpe=None, pos_offset: int = 0):
 # The workspace budget is a quarter of the HBM the device can still give (utils/memory.py),
 # capped at those 8 GiB and floored at 256 MiB; PLLM_CE_WORKSPACE_MB fixes it instead.
 CE_CHUNK_ROWS = _ab("ce_chunk_rows", 0)
-CE_WORKSPACE_MB = float(_os.environ["PLLM_CE_WORKSPACE_MB"]) if "PLLM_CE_WORKSPACE_MB" in _os.environ else None
+CE_WORKSPACE_MB = float(os.environ["PLLM_CE_WORKSPACE_MB"]) if "PLLM_CE_WORKSPACE_MB" in os.environ else None
 
 
 def _ce_budget_bytes(device) -> int:
@@ -1262,6 +1229,16 @@ def _ce_chunk_rows(N: int, V: int = 50304, budget_bytes: Optional[int] = None) -
     if n_chunks == 1:
         return N
     return max(64, (math.ceil(N / n_chunks) + 63) // 64 * 64)
+
+
+def _logits_into(ws, hc, weight, bias):
+    """One chunk's logits hc W^T (+ bias) written into the head rows of the workspace ``ws``; returns those rows."""
+    lg = ws[:hc.shape[0]]
+    if bias is not None:
+        torch.addmm(bias, hc, weight.t(), out=lg)
+    else:
+        torch.mm(hc, weight.t(), out=lg)
+    return lg
 
 
 class _LMHeadCEFn(torch.autograd.Function):
@@ -1292,15 +1269,11 @@ class _LMHeadCEFn(torch.autograd.Function):
               torch.empty(V, C, dtype=torch.float32, device=h.device)) if need_w else None
         db = torch.zeros(V, dtype=torch.float32, device=h.device) if need_b else None
         rows = torch.empty(N, dtype=torch.float32, device=h.device)
-        wt = getattr(weight, "_pllm_wT", None)
-        wt = wt if wt is not None and getattr(weight, "_pllm_wT_ver", None) == weight._version else None
+        wt = _shadow(weight)
         for r0 in range(0, N, R):
             r1 = min(N, r0 + R)
-            hc, lg = h[r0:r1], ws[:r1 - r0]
-            if bias is not None:
-                torch.addmm(bias, hc, weight.t(), out=lg)
-            else:
-                torch.mm(hc, weight.t(), out=lg)
+            hc = h[r0:r1]
+            lg = _logits_into(ws, hc, weight, bias)
             rows[r0:r1] = _ops().cross_entropy(lg, targets[r0:r1], lg, ignore_index, inv_n)
             if need_h:  # dh = dlogits @ W (through the W^T shadow when present, see _dgrad)
                 torch.mm(lg, wt.t() if wt is not None else weight, out=dh[r0:r1])
@@ -1340,7 +1313,7 @@ class _LMHeadCEFn(torch.autograd.Function):
                 _notify(ctx.w)
             else:
                 gw = dw.mul_(g).to(ctx.wdtype)
-        if db is not None:
+        if db is not None:  # (the forward's column sums scaled by g, not a bias_grad pass: no _bias_param_grad)
             tgt = _acc_target(ctx.b)
             if tgt is not None:
                 tgt.addcmul_(db, g)
@@ -1365,11 +1338,7 @@ def lm_head_cross_entropy(h, weight, bias, targets, ignore_index: int = -100):
         rows = torch.empty(N, dtype=torch.float32, device=h.device)
         for r0 in range(0, N, R):
             r1 = min(N, r0 + R)
-            lg = ws[:r1 - r0]
-            if bias is not None:
-                torch.addmm(bias, h[r0:r1], weight.t(), out=lg)
-            else:
-                torch.mm(h[r0:r1], weight.t(), out=lg)
+            lg = _logits_into(ws, h[r0:r1], weight, bias)
             rows[r0:r1] = _ops().cross_entropy(lg, targets[r0:r1], None, ignore_index)
         return rows.sum() / (targets != ignore_index).sum().clamp_min(1)
     logits = F.linear(h, weight, bias)
