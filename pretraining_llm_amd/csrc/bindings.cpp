@@ -481,16 +481,28 @@ Tensor swiglu_bwd(const Tensor& dy, const Tensor& gu) {
   return dgu;
 }
 
+// what rope and rope_qk share: x bf16 / contiguous / 16-B aligned, fp32 [n_pos, D / 2] tables of ONE shape on
+// x's device (the kernel reads row (r % T) + pos_offset of both), 0 <= pos_offset, T + pos_offset <= n_pos
+void check_rope_args(const Tensor& x, const Tensor& cos, const Tensor& sin, int64_t T, int64_t pos_offset) {
+  check_bf16(x, "x");
+  check_contig(x, "x");
+  check_aligned16(x, "x");
+  TORCH_CHECK(x.dim() >= 1, "rope: x must be [..., heads * D]");
+  TORCH_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat, "rope tables must be fp32");
+  TORCH_CHECK(cos.dim() == 2 && sin.sizes() == cos.sizes(), "rope tables: cos and sin must both be [n_pos, D / 2]");
+  TORCH_CHECK(cos.device() == x.device() && sin.device() == x.device(), "rope tables must be on x's device");
+  TORCH_CHECK(cos.is_contiguous() && sin.is_contiguous(), "rope tables contiguous");
+  TORCH_CHECK(T > 0, "rope: T must be positive");
+  TORCH_CHECK(pos_offset >= 0, "rope: pos_offset must be >= 0, got ", pos_offset);
+}
+
 // packed rows [..., n_heads_total * D]; rotates the first n_rot heads; T = positions per sequence
 // attention pre-pass: the rotated q and k heads of a packed [.., (H + 2 Hkv) D] qkv tensor as one
 // contiguous [.., (H + Hkv) D] buffer (v is not copied)
 Tensor rope_qk(const Tensor& x, const Tensor& cos, const Tensor& sin, int64_t n_heads_total, int64_t n_rot, int64_t T) {
-  check_bf16(x, "x");
-  check_contig(x, "x");
-  TORCH_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat, "rope tables must be fp32");
-  TORCH_CHECK(cos.is_contiguous() && sin.is_contiguous(), "rope tables contiguous");
+  check_rope_args(x, cos, sin, T, 0);
   const int64_t W = x.size(-1);
-  TORCH_CHECK(W % n_heads_total == 0 && n_rot > 0 && n_rot <= n_heads_total, "rope_qk: heads");
+  TORCH_CHECK(n_heads_total > 0 && W % n_heads_total == 0 && n_rot > 0 && n_rot <= n_heads_total, "rope_qk: heads");
   const int64_t D = W / n_heads_total;
   TORCH_CHECK(D % 16 == 0, "rope_qk: head dim must be a multiple of 16");
   TORCH_CHECK(cos.size(-1) == D / 2 && cos.size(0) >= T, "rope_qk: table shape");
@@ -507,12 +519,10 @@ Tensor rope_qk(const Tensor& x, const Tensor& cos, const Tensor& sin, int64_t n_
 
 Tensor rope(const Tensor& x, const Tensor& cos, const Tensor& sin, int64_t n_heads_total, int64_t n_rot, int64_t T,
             int64_t pos_offset, bool inverse) {
-  check_bf16(x, "x");
-  check_contig(x, "x");
-  TORCH_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat, "rope tables must be fp32");
-  TORCH_CHECK(cos.is_contiguous() && sin.is_contiguous(), "rope tables contiguous");
+  check_rope_args(x, cos, sin, T, pos_offset);
   const int64_t W = x.size(-1);
-  TORCH_CHECK(W % n_heads_total == 0, "rope: width not divisible by heads");
+  TORCH_CHECK(n_heads_total > 0 && W % n_heads_total == 0, "rope: width not divisible by heads");
+  TORCH_CHECK(n_rot >= 0 && n_rot <= n_heads_total, "rope: n_rot must be in [0, n_heads_total], got ", n_rot);
   const int64_t D = W / n_heads_total;
   TORCH_CHECK(D % 16 == 0, "rope: head dim must be a multiple of 16");
   TORCH_CHECK(cos.size(-1) == D / 2 && cos.size(0) >= T + pos_offset, "rope: table shape");
@@ -773,11 +783,14 @@ Tensor grad_norm_clip(const Tensor& x, double grad_scale, double max_norm) {
 Tensor embedding_fwd(const Tensor& idx, const Tensor& wte, const std::optional<Tensor>& wpe, int64_t pos_offset) {
   check_bf16(wte, "wte");
   TORCH_CHECK(idx.is_cuda() && idx.dim() == 2, "idx must be [B, T] on GPU");
+  TORCH_CHECK(wte.dim() == 2, "embedding: wte must be [V, C]");
+  TORCH_CHECK(pos_offset >= 0, "embedding: pos_offset must be >= 0, got ", pos_offset);
   const int64_t C = wte.size(1), T = idx.size(1);
   TORCH_CHECK(C % 8 == 0 && wte.is_contiguous(), "embedding: C % 8");
   if (wpe) {
     check_bf16(*wpe, "wpe");
-    TORCH_CHECK(wpe->size(1) == C && wpe->size(0) >= T + pos_offset && wpe->is_contiguous(), "wpe shape");
+    TORCH_CHECK(wpe->dim() == 2 && wpe->size(1) == C && wpe->size(0) >= T + pos_offset && wpe->is_contiguous(),
+                "wpe shape");
   }
   Tensor ix = idx.to(at::kLong).contiguous();
   Tensor out = at::empty({idx.size(0), T, C}, wte.options());
@@ -793,6 +806,7 @@ std::vector<Tensor> embedding_bwd(const Tensor& dx, const Tensor& idx, int64_t V
                                   const std::optional<Tensor>& dwte_acc, const std::optional<Tensor>& dwpe_acc) {
   check_bf16(dx, "dx");
   check_contig(dx, "dx");
+  TORCH_CHECK(idx.dim() == 2, "embedding bwd: idx must be [B, T]");
   const int64_t Bn = idx.size(0), T = idx.size(1), C = dx.size(-1);
   TORCH_CHECK(dx.numel() == Bn * T * C, "embedding bwd shape");
   TORCH_CHECK(!has_wpe || n_pos >= T, "embedding bwd: n_pos < T");
