@@ -169,10 +169,10 @@ Tensor bias_grad(const Tensor& dy, const std::optional<Tensor>& out_acc) {
 
 // ---------------------------------------------------------------- weight-gradient GEMM
 // out[P, Q] (+)= dy[M, P]^T @ x[M, Q]; accumulates into out_acc if given, else returns a new tensor.
+// overwrite (with out_acc): store dW into out_acc instead of adding (its first write of a step).
 // bias_acc (requires out_acc): the bias gradient column sums of dy are added into it too -- inside the
-// GEMM when its kernel can (wgrad_kernel's all-ones MFMAs), else by the bias_grad kernels
-Tensor bias_grad(const Tensor& dy, const std::optional<Tensor>& out_acc);
-// overwrite (with out_acc): store dW into out_acc instead of adding (its first write of a step)
+// GEMM when its kernel can (WgradPlan::fused_bias), else by the bias_grad kernels.
+// Kernel, grid and both workspaces come from one WgradPlan (gemm_plan.h).
 Tensor wgrad(const Tensor& dy, const Tensor& x, const std::optional<Tensor>& out_acc,
              const std::optional<Tensor>& bias_acc, bool overwrite) {
   check_bf16(dy, "dy");
@@ -184,34 +184,27 @@ Tensor wgrad(const Tensor& dy, const Tensor& x, const std::optional<Tensor>& out
   TORCH_CHECK(M % 64 == 0, "wgrad: M (tokens) must be a multiple of 64");
   check_aligned16(dy, "dy");
   check_aligned16(x, "x");
-  Tensor out;
-  bool of32 = false;
+  bool of32 = false, bf32 = false;
   if (out_acc) {
     of32 = check_grad(*out_acc, "out_acc");
     TORCH_CHECK(out_acc->numel() == P * Q && out_acc->is_contiguous(), "wgrad: out_acc shape");
     check_aligned16(*out_acc, "out_acc");
-    out = *out_acc;
-  } else {
-    out = at::empty({P, Q}, dy.options());
   }
-  int S = 1, slice = 1;
-  pllm::wgrad_plan((int)M, (int)P, (int)Q, &S, &slice);
-  const bool of32_pre = out_acc && out_acc->scalar_type() == at::kFloat;
-  Tensor part = at::empty({std::max<int64_t>(pllm::wgrad_ws_floats((int)M, (int)P, (int)Q, of32_pre,
-                                                                   bias_acc.has_value()), 1)},
-                          dy.options().dtype(at::kFloat));
-  bool bf32 = false;
-  Tensor bpart;
   if (bias_acc) {
     TORCH_CHECK(out_acc.has_value(), "wgrad: bias_acc needs out_acc");
     bf32 = check_grad(*bias_acc, "bias_acc");
     TORCH_CHECK(bias_acc->numel() == P && bias_acc->is_contiguous(), "wgrad: bias_acc [P]");
     check_aligned16(*bias_acc, "bias_acc");
-    bpart = at::empty({S, P}, dy.options().dtype(at::kFloat));
   }
+  const pllm::WgradPlan plan = pllm::wgrad_plan(pllm::gemm_settings(), pllm::gemm_cus(), (int)M, (int)P, (int)Q, of32,
+                                                bias_acc.has_value());
+  auto f32 = dy.options().dtype(at::kFloat);
+  Tensor out = out_acc ? *out_acc : at::empty({P, Q}, dy.options());
+  Tensor part = at::empty({std::max<int64_t>(plan.ws_floats, 1)}, f32);
+  Tensor bpart = bias_acc ? at::empty({plan.bias_rows, P}, f32) : Tensor();
   bool fused_b = false;
   if (M > 0)
-    fused_b = pllm::wgrad(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), (int)M, (int)P, (int)Q,
+    fused_b = pllm::wgrad(plan, dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), (int)M, (int)P, (int)Q,
                           part.data_ptr<float>(), out.data_ptr(), of32, out_acc.has_value() && !overwrite,
                           cur_stream(), bias_acc ? bpart.data_ptr<float>() : nullptr,
                           bias_acc ? bias_acc->data_ptr() : nullptr, bf32);
@@ -237,7 +230,9 @@ std::tuple<Tensor, Tensor> gemm_tn(const Tensor& a, const Tensor& b, const std::
   const int64_t M = a.size(0), K = a.size(1), N = epi == 7 ? b.size(0) / 2 : b.size(0);
   // epi 7: b = [gate | up] rows [2F, K] -> out = silu(gate) * up [M, F], aux = [gate | up] [M, 2F]
   // (the llama up-projection with its SwiGLU; ping-pong kernel only)
-  TORCH_CHECK(epi != 7 || (b.size(0) % 16 == 0 && pllm::gemm_uses_pp((int)K, 7, 0)),
+  const pllm::GemmPlan plan = pllm::gemm_plan(pllm::gemm_settings(), pllm::gemm_cus(), (int)M, (int)N, (int)K, (int)epi,
+                                              (int)T);
+  TORCH_CHECK(epi != 7 || (b.size(0) % 16 == 0 && plan.pp),
               "gemm_tn: epi 7 needs 2F % 16 == 0, K >= 128 and the ping-pong kernel");
   TORCH_CHECK(K % 64 == 0 && K > 0, "gemm_tn: K must be a positive multiple of 64, got ", K);
   TORCH_CHECK(N % 8 == 0 && a.stride(0) % 8 == 0, "gemm_tn: N and lda must be multiples of 8");
@@ -303,7 +298,7 @@ std::tuple<Tensor, Tensor> gemm_tn(const Tensor& a, const Tensor& b, const std::
     check_aligned16(*aux, "aux");
     g.aux = (uint16_t*)aux->data_ptr();
     g.ldaux = aux->stride(0);
-    part = at::empty({pllm::gemm_colsum_groups((int)M, (int)K), N}, a.options().dtype(at::kFloat));
+    part = at::empty({plan.colsum_groups, N}, a.options().dtype(at::kFloat));
     g.colpart = part.data_ptr<float>();
   }
   bool of32 = false;
@@ -313,10 +308,9 @@ std::tuple<Tensor, Tensor> gemm_tn(const Tensor& a, const Tensor& b, const std::
     TORCH_CHECK(bias_acc->numel() == N && bias_acc->is_contiguous(), "gemm_tn: bias_acc [N]");
   }
   if (M > 0) {
-    pllm::gemm_tn(g, (int)epi, cur_stream());
+    pllm::gemm_tn(g, plan, (int)epi, cur_stream());
     if (bias_acc)
-      pllm::col_reduce(g.colpart, pllm::gemm_colsum_groups((int)M, (int)K), (int)N, bias_acc->data_ptr(), of32, true,
-                       cur_stream());
+      pllm::col_reduce(g.colpart, plan.colsum_groups, (int)N, bias_acc->data_ptr(), of32, true, cur_stream());
   }
   return {out, aux_out};  // a (Tensor, Tensor) tuple: functionalization rejects Tensor[] beside an (a!) arg
 }
@@ -1208,29 +1202,27 @@ TORCH_LIBRARY(pllm, m) {
   m.def("bias_grad(Tensor dy, Tensor(a!)? out_acc=None) -> Tensor");
   m.def("wgrad(Tensor dy, Tensor x, Tensor(a!)? out_acc=None, Tensor(b!)? bias_acc=None, bool overwrite=False) -> Tensor");
   m.def("gemm_tn(Tensor a, Tensor b, Tensor? bias, int epi, Tensor? aux=None, Tensor(a!)? bias_acc=None, int T=0) -> (Tensor, Tensor)");
-  m.def("gemm_uses_pp(int K, int epi) -> bool", [](int64_t K, int64_t epi) { return pllm::gemm_uses_pp((int)K, (int)epi, 16); });
-  // read-only views of the dispatch under the current settings (the tests assert the arm a case was written for):
+  m.def("gemm_uses_pp(int K, int epi) -> bool", [](int64_t K, int64_t epi) {
+    return pllm::gemm_plan(pllm::gemm_settings(), pllm::gemm_cus(), 0, 0, (int)K, (int)epi, 16).pp;
+  });
+  // read-only views of the plans gemm_tn / wgrad run under the current settings (the tests assert the arm a case
+  // was written for):
   // gemm_plan -> [ping-pong kernel, quadrant epilogues, workgroups, tile rows, tile columns, column-sum
   // partial rows of epi 3 / 4]; N as gemm_tn takes it (epi 7: F)
   m.def("gemm_plan(int M, int N, int K, int epi, int T=0) -> int[]",
         [](int64_t M, int64_t N, int64_t K, int64_t epi, int64_t T) {
-          const bool pp = pllm::gemm_uses_pp((int)K, (int)epi, (int)T);
-          const int64_t tm = (M + 255) / 256, tn = pp && epi == 7 ? (N + 127) / 128 : (N + 255) / 256;
-          return std::vector<int64_t>{pp, pp && pllm::gemm_pp_quad_epilogue((int)K, (int)epi),
-                                      std::min<int64_t>(tm * tn, pllm::gemm_grid_cap()), tm, tn,
-                                      pllm::gemm_colsum_groups((int)M, (int)K)};
+          const pllm::GemmPlan p =
+              pllm::gemm_plan(pllm::gemm_settings(), pllm::gemm_cus(), (int)M, (int)N, (int)K, (int)epi, (int)T);
+          return std::vector<int64_t>{p.pp, p.quad, p.grid, p.tiles_m, p.tiles_n, p.colsum_groups};
         });
-  // wgrad_plan -> [arm (wgrad_arm: 0 / 1 one-barrier kernel 16x16x32 / 32x32x16, 2 ping-pong, 3 hybrid), S,
+  // wgrad_plan -> [arm (0 / 1 one-barrier kernel 16x16x32 / 32x32x16, 2 ping-pong, 3 hybrid), S,
   // slice (tokens), then the hybrid form's whole tiles, sliced tiles, their slice count and K-tiles per slice
   // (zeros on the other arms)]
   m.def("wgrad_plan(int M, int P, int Q, bool out_f32, bool bias) -> int[]",
         [](int64_t M, int64_t P, int64_t Q, bool of32, bool bias) {
-          int S = 1, slice = 1, full = 0, rem = 0, hs = 0, skt = 0;
-          pllm::wgrad_plan((int)M, (int)P, (int)Q, &S, &slice);
-          const int arm = pllm::wgrad_arm((int)M, (int)P, (int)Q, of32, bias);
-          if (arm != 3 || !pllm::wgrad_hy_plan((int)M, (int)P, (int)Q, pllm::gemm_grid_cap(), &full, &rem, &hs, &skt))
-            full = rem = hs = skt = 0;
-          return std::vector<int64_t>{arm, S, slice, full, rem, hs, skt};
+          const pllm::WgradPlan p =
+              pllm::wgrad_plan(pllm::gemm_settings(), pllm::gemm_cus(), (int)M, (int)P, (int)Q, of32, bias);
+          return std::vector<int64_t>{p.arm, p.S, p.slice, p.hy_full, p.hy_rem, p.hy_s, p.hy_slice_kt};
         });
   m.def("gemm_set_config(int mfma, int group_m, int phased=-1, int reserve_cus=-1, int persistent=-1) -> ()",
         [](int64_t mf, int64_t gm, int64_t ph, int64_t rc, int64_t pe) {

@@ -35,6 +35,7 @@
 // Requires K % 64 == 0, N % 8 == 0, lda / ldb / ldc / ldaux % 8 == 0 (checked by the binding).
 #include <type_traits>
 
+#include "ab.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -362,44 +363,21 @@ __global__ __launch_bounds__(GNT) void gemm_tn_kernel(pllm::GemmArgs g) {
 
 namespace pllm {
 
-static int g_gemm_mfma = 16;
-#ifndef PL_GEMM_GROUP_M
-#define PL_GEMM_GROUP_M 4  // m-tiles per tile group (L2 reuse of the B panels; A/B builds)
-#endif
-static int g_gemm_group_m = PL_GEMM_GROUP_M;
-// 0: every wave issues its DMA pieces; 2: the asymmetric DMA (waves 0-3 issue all).  Measured and
-// removed (profiles/r3_gemm_tn.md): 1 = two k32 phases per K-tile with counted vmcnt across raw
-// barriers (3-12 % slower), 3 = one wave per SIMD with 128x128 per wave and the DMA pinned between
-// MFMA groups (hipBLASLt's geometry; 4-18 % slower, its fused epilogues up to 40 % slower)
-// 4 (default): the ping-pong kernel of gemm_pp.hip (two wave groups one barrier apart, counted
-// waits): 4-6 % faster than this file's kernel on every fused epilogue measured (GELU' / SwiGLU' /
-// attention delta; profiles/r4_gemm_pp.md), whole GPT-2 step +0.5 %.
-// This file's kernel is the FALLBACK for what the ping-pong loop does not take (a single K-tile,
-// K < 128; the delta epilogue with T % 16 != 0); 0 / 2 select it for every shape (tests only).  Its
-// 32x32x16 and asymmetric-DMA instantiations run only under gemm_set_config from the tests.
-static int g_gemm_phased = 4;
-// CUs the persistent grids leave free, for RCCL kernels overlapping the backward (world > 1)
-static int g_gemm_reserve = 0;
-// 0: the persistent kernels (gemm_pp / wgrad_pp / this file's) launch one workgroup per tile instead
-// of one per CU, so the hardware deals tiles to whichever CUs are free (e.g. beside RCCL kernels)
-static int g_gemm_persistent = 1;
+static_assert(GT == kPlanTile, "gemm_plan.h counts this kernel's tiles");
+
+// the dispatch settings of the GEMM family (defaults and their records: gemm_plan.h)
+static GemmSettings g_settings;
+const GemmSettings& gemm_settings() {
+  g_settings.wgrad_hy_cost = ab_int("wgrad_hy_cost", 1);
+  return g_settings;
+}
 void gemm_set_config(int mfma, int group_m, int phased, int reserve_cus, int persistent) {
-  if (mfma == 16 || mfma == 32) g_gemm_mfma = mfma;
-  if (group_m > 0) g_gemm_group_m = group_m;
-  if (phased >= 0) g_gemm_phased = phased;
-  if (reserve_cus >= 0) g_gemm_reserve = reserve_cus;
-  if (persistent >= 0) g_gemm_persistent = persistent;
+  g_settings.set_config(mfma, group_m, phased, reserve_cus, persistent);
 }
+void wgrad_set_mfma(int mf) { g_settings.set_wgrad_mfma(mf); }
+void wgrad_set_hy(int on) { g_settings.wgrad_hy = on; }
 
-// column-sum partial rows of the EPI 3 / 4 bias gradient: 2 per tile row here, 4 (one per
-// accumulator quadrant row half and wave row) in the ping-pong kernel's quadrant epilogues
-// the ping-pong kernel serves a call when selected, with >= 2 K-tiles and (epilogue 6) 16 | T
-bool gemm_uses_pp(int K, int epi, int T) { return g_gemm_phased == 4 && K >= 128 && (epi != 6 || T % 16 == 0); }
-int gemm_colsum_groups(int M, int K) {
-  return gemm_uses_pp(K, 3, 0) ? gemm_pp_colsum_groups(M, K) : 2 * ((M + GT - 1) / GT);
-}
-
-static int num_cus() {
+int gemm_cus() {
   static int n = 0;
   if (n == 0) {
     int dev = 0;
@@ -409,28 +387,18 @@ static int num_cus() {
   return n;
 }
 
-static int gemm_ctas() {
-  // persistent grid: one workgroup per CU, minus the CUs reserved for concurrent collectives;
-  // non-persistent: no cap (one workgroup per tile / work item)
-  if (!g_gemm_persistent) return 1 << 30;
-  return num_cus() - g_gemm_reserve > 8 ? num_cus() - g_gemm_reserve : 8;
-}
-int gemm_grid_cap() { return gemm_ctas(); }
-
-void gemm_tn(const GemmArgs& a0, int epi, hipStream_t st) {
+void gemm_tn(const GemmArgs& a0, const GemmPlan& p, int epi, hipStream_t st) {
+  if (p.grid == 0) return;
   GemmArgs a = a0;
-  a.group_m = g_gemm_group_m;
-  const int ntiles = ((a.M + GT - 1) / GT) * ((a.N + GT - 1) / GT);
-  if (ntiles == 0) return;
-  const int ctas = gemm_ctas();
-  if (gemm_uses_pp(a.K, epi, a.T)) {
-    gemm_tn_pp(a, epi, ctas, st);
+  a.group_m = g_settings.group_m;
+  if (p.pp) {
+    gemm_tn_pp(a, p, epi, st);
     return;
   }
-  const int tiles = ntiles < ctas ? ntiles : ctas;
+  const int tiles = p.grid;
 #define PL_GEMM_CASE(MFV, E)                                                       \
   do {                                                                               \
-    if (g_gemm_phased == 2)                                                          \
+    if (g_settings.phased == 2)                                                      \
       hipLaunchKernelGGL((gemm_tn_kernel<MFV, E, true>), dim3(tiles), dim3(GNT), 0, st, a); \
     else                                                                             \
       hipLaunchKernelGGL((gemm_tn_kernel<MFV, E, false>), dim3(tiles), dim3(GNT), 0, st, a); \
@@ -445,7 +413,7 @@ void gemm_tn(const GemmArgs& a0, int epi, hipStream_t st) {
     case 5: PL_GEMM_CASE(MFV, 5); break; \
     default: PL_GEMM_CASE(MFV, 6); break; \
   }
-  if (g_gemm_mfma == 16) {
+  if (g_settings.mfma == 16) {
     PL_GEMM_EPIS(16)
   } else {
     PL_GEMM_EPIS(32)

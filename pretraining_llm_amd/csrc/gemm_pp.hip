@@ -1,7 +1,7 @@
 // Ping-pong TN GEMM with fused epilogues on gfx950 MFMA (round 4):
 //     C[M, N] = epi( A[M, K] . B[N, K]^T )          (bf16 in, fp32 accumulate, bf16 out)
 // Same contract and epilogues as gemm_tn_kernel (csrc/gemm.hip, the fallback for the calls this
-// kernel does not take -- a single K-tile, or epilogue 6 with T % 16 != 0: gemm_uses_pp -- and the
+// kernel does not take -- a single K-tile, or epilogue 6 with T % 16 != 0: GemmPlan::pp -- and the
 // tests' A/B reference); a structurally different main loop, built for the measured bottleneck of
 // that kernel: its waves parked 36 % of the time on the one barrier + vmcnt(0) per 64-deep K-tile
 // (profiles/r3_gemm_tn.md: MFMA busy 41 % vs hipBLASLt's 52 %).  Reference math: the MLP and
@@ -66,7 +66,7 @@ PL_DEV void pp_vmwait() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// Two epilogue placements (template flag QE, chosen per call by gemm_pp_quad_epilogue):
+// Two epilogue placements (template flag QE, chosen per call by GemmPlan::quad):
 //  * end of tile (QE = false): the vector-memory instructions it issues after its last wait
 //    (its stores; a lower bound) are what the counted waits of the next tile's first phases
 //    leave outstanding;
@@ -455,7 +455,7 @@ PL_DEV void pp_aux_issue(const PPCtx& c, const PPEpi& e) {
 // The epilogue of quadrant Q of tile e (its aux / bias already in the wave's LDS area and read
 // into ax).  EPI 6's delta needs both column pairs of a row: dsum carries pair 0's partial to
 // the pair-1 quadrant that follows it.  EPI 3 / 4 write the quadrant's column sums to colpart
-// row 4 tm + 2 wr + jh (gemm_colsum_groups = 4 per tile row with this kernel).
+// row 4 tm + 2 wr + jh (GemmPlan::colsum_groups = 4 per tile row with this kernel).
 template <int EPI, int Q>
 PL_DEV void pp_epi_quad(f32x4 (&acc)[4][8], const PPCtx& c, const PPEpi& e, const u32x4 (&ax)[4],
                           float (&dsum)[4]) {
@@ -831,21 +831,12 @@ __global__ __launch_bounds__(PNT) void gemm_pp_kernel(pllm::GemmArgs g) {
 
 namespace pllm {
 
-// EPI 3 / 4 column-sum partial rows: 4 per tile row with quadrant epilogues, 2 otherwise
-int gemm_pp_colsum_groups(int M, int K) { return (gemm_pp_quad_epilogue(K, 3) ? 4 : 2) * ((M + PT - 1) / PT); }
+static_assert(PT == kPlanTile && kNT<7> == kPlanTileNSwiglu, "gemm_plan.h counts this kernel's tiles");
 
-// quadrant epilogues at K >= 2048, except EPI 5 (aux too large for the LDS) and EPI 1 (the GELU's
-// VALU work in the LOAD segments: 1410 vs 1344 us for the end-of-tile form + hipBLASLt at the llama
-// shape 32768 x 11008 x 2048, gpurun_out/r4pp7_bench.jsonl)
-// (EPI 7 has no quadrant form either: its instantiation below is always the end-of-tile one)
-bool gemm_pp_quad_epilogue(int K, int epi) { return K >= 2048 && epi != 5 && epi != 1 && epi != 7; }
-
-void gemm_tn_pp(const GemmArgs& a, int epi, int ctas, hipStream_t st) {
-  const int nt = epi == 7 ? 128 : PT;
-  const int ntiles = ((a.M + PT - 1) / PT) * ((a.N + nt - 1) / nt);
-  if (ntiles == 0) return;
-  const int grid = ntiles < ctas ? ntiles : ctas;
-  const bool qe = gemm_pp_quad_epilogue(a.K, epi);
+void gemm_tn_pp(const GemmArgs& a, const GemmPlan& p, int epi, hipStream_t st) {
+  const int grid = p.grid;
+  if (grid == 0) return;
+  const bool qe = p.quad;
 #define PL_PP_CASE(E)                                                                          \
   do {                                                                                           \
     if (qe) hipLaunchKernelGGL((gemm_pp_kernel<E, E != 5 && E != 1>), dim3(grid), dim3(PNT), 0, st, a); \

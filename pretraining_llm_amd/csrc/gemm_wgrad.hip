@@ -305,132 +305,40 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 
 namespace pllm {
 
-// Variant selection (wgrad_set_mfma): 0 = default -- the ping-pong kernel of wgrad_pp.hip where it
-// applies (fp32 gradient target), else this file's kernel per shape; 100 = this file's kernel per
-// shape (as does any other non-zero value); 16 / 32 = this file's kernel with that MFMA shape.
-// Same-box A/B of the MFMA shapes (profiles/r3_wgrad_asym_ab.md): 16x16x32 wins everywhere except the
-// LM-head shapes (P = vocabulary), where 32x32x16 does (+0.5-4 %)
-static int g_wgrad_mfma = 0;  // 0: per shape
-static bool g_wgrad_pp = true;
-void wgrad_set_mfma(int mf) {
-  g_wgrad_pp = mf == 0;
-  g_wgrad_mfma = (mf == 16 || mf == 32) ? mf : 0;
+static_assert(BT == kPlanTile && BKM == kPlanKTile, "gemm_plan.h counts this kernel's tiles and stages");
+
+// out[n] (+)= the S rows part[S][n] in row order
+static void wgrad_reduce(const float* part, int S, int64_t n, void* out, bool out_f32, bool accumulate,
+                         hipStream_t st) {
+  const dim3 grid((unsigned)((n / 8 + 255) / 256));
+  if (out_f32) hipLaunchKernelGGL(wgrad_reduce_kernel<true>, grid, dim3(256), 0, st, part, S, n, out, (int)accumulate);
+  else hipLaunchKernelGGL(wgrad_reduce_kernel<false>, grid, dim3(256), 0, st, part, S, n, out, (int)accumulate);
 }
 
-void wgrad_plan(int M, int P, int Q, int* S, int* slice) {
-  // Split-K slice count from a cost model: rounds of 256 workgroups (one per CU) x stages per
-  // slice x ~2.0 us per 256x256x64 stage, plus -- for S > 1 -- the fp32 slab traffic (S slabs
-  // written by the main kernel and read back by the reduce) at ~4 TB/s.  The slab term is what
-  // keeps S small when P x Q is large (llama MLP: 11008 x 2048 at 16K tokens -> S = 2, not 11).
-  // >= 8 stages per slice; near-ties (< 2 %) go to fewer slices.
-  const int ntiles = ((P + BT - 1) / BT) * ((Q + BT - 1) / BT);
-  const int kst = M / BKM;
-  int best = 1;
-  double best_t = 1e30, best_eff = 0.0;
-  for (int s = 1; s <= 64; ++s) {
-    if (s > 1 && kst / s < 8) break;
-    const int n = ntiles * s;
-    const int rounds = (n + 255) / 256;
-    const int st_per = (kst + s - 1) / s;
-    double t = rounds * (double)st_per * 2.0e-6;
-    if (s > 1) t += (double)P * Q * 4.0 * (2 * s + 1) / 4.0e12;
-    if (t < best_t * 0.98) {
-      best_t = t;
-      best = s;
-    }
-  }
-  int st_per = (kst + best - 1) / best;
-  *slice = st_per * BKM;
-  *S = (kst + st_per - 1) / st_per;
-}
-
-int wgrad_bias_slices(int M, int P, int Q) {
-  int S, slice;
-  wgrad_plan(M, P, Q, &S, &slice);
-  return S;
-}
-
-// hybrid weight gradients (wgrad_pp_hy), default on: with more tiles than CUs, whole tiles for the whole
-// rounds and slices only for the last one -- LM head 65536 x 50304 x 768 3,984 vs 4,081 us, 32768 x 50304 x
-// 2048 5,190 vs 5,721 us, GPT-2 step +0.3 %, llama +0.2-0.3 % (profiles/r4_wgrad_hybrid.md).  On the
-// persistent grid only (whole rounds of one tile per CU); with a grid per tile the hardware deals the tiles
-// anyway.  (Full stream-K -- equal K-tile runs per workgroup -- lost 13-47 %: r4_wgrad_stream_k_negative.md)
-static int g_wgrad_hy = 1;
-void wgrad_set_hy(int on) { g_wgrad_hy = on; }
-
-static bool wgrad_use_hy(int M, int P, int Q, bool out_f32, bool bias) {
-  int full, rem, S, skt;
-  return g_wgrad_hy && g_wgrad_pp && out_f32 && !bias && gemm_grid_cap() < (1 << 29) &&
-         wgrad_hy_plan(M, P, Q, gemm_grid_cap(), &full, &rem, &S, &skt);
-}
-
-int64_t wgrad_ws_floats(int M, int P, int Q, bool out_f32, bool bias) {
-  if (wgrad_use_hy(M, P, Q, out_f32, bias)) return wgrad_pp_hy_ws_floats(M, P, Q, gemm_grid_cap());
-  int S, slice;
-  wgrad_plan(M, P, Q, &S, &slice);
-  return S > 1 ? (int64_t)S * P * Q : 0;
-}
-
-int wgrad_arm(int M, int P, int Q, bool out_f32, bool bias) {
-  if (wgrad_use_hy(M, P, Q, out_f32, bias)) return 3;
-  int S, slice;
-  wgrad_plan(M, P, Q, &S, &slice);
-  if (g_wgrad_pp && out_f32 && wgrad_pp_supported(M, P, Q, S, slice)) return 2;
-  return (g_wgrad_mfma != 0 ? g_wgrad_mfma : (P >= 16384 ? 32 : 16)) == 16 ? 0 : 1;
-}
-
-bool wgrad(const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P, int Q, float* part, void* out,
-           bool out_f32, bool accumulate, hipStream_t st, float* bpart, void* bout, bool bout_f32) {
-  const int arm = wgrad_arm(M, P, Q, out_f32, bpart != nullptr && bout != nullptr);
-  if (arm == 3) {
-    wgrad_pp_hy(dy, lda, x, ldb, M, P, Q, part, (float*)out, accumulate, gemm_grid_cap(), st);
-    return false;
-  }
-  int S, slice;
-  wgrad_plan(M, P, Q, &S, &slice);
-  const int ntiles = ((P + BT - 1) / BT) * ((Q + BT - 1) / BT);
-  if (arm == 2) {
-    const bool fb = bpart != nullptr && bout != nullptr;
-    wgrad_pp(dy, lda, x, ldb, M, P, Q, S, slice, part, (float*)out, accumulate, fb ? bpart : nullptr,
-             gemm_grid_cap(), st);
-    if (fb) {
-      const dim3 bg((unsigned)((P / 8 + 255) / 256));
-      if (bout_f32) hipLaunchKernelGGL(wgrad_reduce_kernel<true>, bg, dim3(256), 0, st, bpart, S, (int64_t)P, bout, 1);
-      else hipLaunchKernelGGL(wgrad_reduce_kernel<false>, bg, dim3(256), 0, st, bpart, S, (int64_t)P, bout, 1);
-    }
-    if (S > 1) {
-      const int64_t PQ = (int64_t)P * Q;
-      const dim3 rg((unsigned)((PQ / 8 + 255) / 256));
-      hipLaunchKernelGGL(wgrad_reduce_kernel<true>, rg, dim3(256), 0, st, part, S, PQ, out, (int)accumulate);
-    }
-    return fb;
-  }
-  const int mfma = arm == 0 ? 16 : 32;
-  // the bias gradient rides along only on the 16x16x32 kernel (see wgrad_kernel)
-  const bool fuse_b = bpart != nullptr && bout != nullptr && mfma == 16;
-  float* const bp = fuse_b ? bpart : nullptr;
-#define PL_WGRAD_LAUNCH(MFV, OF)                                                                           \
-  hipLaunchKernelGGL((wgrad_kernel<MFV, OF>), dim3(ntiles * S), dim3(NT), 0, st, (const uint16_t*)dy, lda, \
-                     (const uint16_t*)x, ldb, M, P, Q, S, slice, part, out, (int)accumulate, bp)
-  if (mfma == 16) {
-    if (out_f32) PL_WGRAD_LAUNCH(16, true);
-    else PL_WGRAD_LAUNCH(16, false);
+bool wgrad(const WgradPlan& p, const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P, int Q,
+           float* part, void* out, bool out_f32, bool accumulate, hipStream_t st, float* bpart, void* bout,
+           bool bout_f32) {
+  float* const bp = p.fused_bias ? bpart : nullptr;
+  if (p.arm >= 2) {
+    wgrad_pp(p, dy, lda, x, ldb, M, P, Q, part, (float*)out, accumulate, bp, st);
+    if (p.arm == 3) return false;  // whole tiles written in place, the sliced ones by wgrad_pp's fix-up
   } else {
-    if (out_f32) PL_WGRAD_LAUNCH(32, true);
-    else PL_WGRAD_LAUNCH(32, false);
-  }
+#define PL_WGRAD_LAUNCH(MFV, OF)                                                                         \
+  hipLaunchKernelGGL((wgrad_kernel<MFV, OF>), dim3(p.grid), dim3(NT), 0, st, (const uint16_t*)dy, lda, \
+                     (const uint16_t*)x, ldb, M, P, Q, p.S, p.slice, part, out, (int)accumulate, bp)
+    if (p.arm == 0) {
+      if (out_f32) PL_WGRAD_LAUNCH(16, true);
+      else PL_WGRAD_LAUNCH(16, false);
+    } else {
+      if (out_f32) PL_WGRAD_LAUNCH(32, true);
+      else PL_WGRAD_LAUNCH(32, false);
+    }
 #undef PL_WGRAD_LAUNCH
-  if (fuse_b) {  // bias gradient: the [S][P] partial rows summed in slice order into bout
-    const dim3 bg((unsigned)((P / 8 + 255) / 256));
-    if (bout_f32) hipLaunchKernelGGL(wgrad_reduce_kernel<true>, bg, dim3(256), 0, st, bpart, S, (int64_t)P, bout, 1);
-    else hipLaunchKernelGGL(wgrad_reduce_kernel<false>, bg, dim3(256), 0, st, bpart, S, (int64_t)P, bout, 1);
   }
-  if (S == 1) return fuse_b;
-  const int64_t PQ = (int64_t)P * Q;
-  const dim3 rg((unsigned)((PQ / 8 + 255) / 256));
-  if (out_f32) hipLaunchKernelGGL(wgrad_reduce_kernel<true>, rg, dim3(256), 0, st, part, S, PQ, out, (int)accumulate);
-  else hipLaunchKernelGGL(wgrad_reduce_kernel<false>, rg, dim3(256), 0, st, part, S, PQ, out, (int)accumulate);
-  return fuse_b;
+  // bias gradient: the [S][P] partial rows summed in slice order into bout; dW: the S slabs into out
+  if (p.fused_bias) wgrad_reduce(bpart, p.S, P, bout, bout_f32, true, st);
+  if (p.S > 1) wgrad_reduce(part, p.S, (int64_t)P * Q, out, out_f32, accumulate, st);
+  return p.fused_bias;
 }
 
 }  // namespace pllm

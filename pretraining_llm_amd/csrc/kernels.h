@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gemm_plan.h"
+
 struct AttnFwdArgs {
   const uint16_t *q, *k, *v;
   uint16_t* o;
@@ -126,9 +128,8 @@ int64_t embedding_bwd_chunks(int64_t N);  // fp32 workspace: 2 * chunks * C floa
 void embedding_bwd(const void* dx, const int32_t* sorted, const int32_t* perm, void* dwte, void* dwpe, bool grad_f32,
                    float* part, int64_t N, int Bn, int T, int C, int64_t V, hipStream_t st);
 
-// gemm.hip: C[M,N] = epi(A[M,K] B[N,K]^T); epi 0 plain (+bias), 1 GELU (aux <- pre-activation),
-// 2 ReLU, 3 GELU backward (aux = pre-activation in), 4 ReLU backward (aux = ReLU output in);
-// 3 / 4 write column sums of C to colpart [gemm_colsum_groups(M)][N] (fp32)
+// gemm.hip / gemm_pp.hip: C[M,N] = epi(A[M,K] B[N,K]^T), epi 0..7 as listed at the top of gemm.hip;
+// 3 / 4 write column sums of C to colpart [GemmPlan::colsum_groups][N] (fp32)
 struct GemmArgs {
   const uint16_t* A;
   const uint16_t* B;
@@ -142,44 +143,32 @@ struct GemmArgs {
   float* delta;  // epilogue 6: [M / T, N / 64, T] row sums of C * aux per 64-column head
   int T;         // epilogue 6: rows per sequence
 };
-void gemm_tn(const GemmArgs& a, int epi, hipStream_t st);
+// The dispatch settings (gemm_plan.h) and the device's CU count: what gemm_plan / wgrad_plan take.
+// gemm_settings() re-reads the PLLM_AB key wgrad_hy_cost on every call.
+const GemmSettings& gemm_settings();
+int gemm_cus();
 // phased: 0 single-phase, 2 asym DMA, 4 ping-pong kernel (gemm_pp.hip); reserve_cus >= 0: CUs left
 // free by the persistent grids (collectives in flight), -1 keeps the current setting
 void gemm_set_config(int mfma, int group_m, int phased, int reserve_cus = -1, int persistent = -1);
-// workgroup cap of the persistent GEMM grids (CUs minus reserve_cus; 2^30 when non-persistent)
-int gemm_grid_cap();
-void gemm_tn_pp(const GemmArgs& a, int epi, int ctas, hipStream_t st);  // gemm_pp.hip
-int gemm_pp_colsum_groups(int M, int K);
-bool gemm_pp_quad_epilogue(int K, int epi);
-int gemm_colsum_groups(int M, int K);  // column-sum partial rows (epi 3 / 4) of the kernel serving K
-bool gemm_uses_pp(int K, int epi, int T);
-// gemm_wgrad.hip: dW[P,Q] (+)= dY[M,P]^T X[M,Q]; part: fp32 [S, P, Q] workspace (wgrad_plan)
-void wgrad_plan(int M, int P, int Q, int* S, int* slice);
 // 0: default dispatch; 16 / 32: gemm_wgrad.hip's kernel with that MFMA shape; any other value (100): that
 // kernel with the MFMA shape chosen per problem
 void wgrad_set_mfma(int mf);
-// bpart / bout (optional): also the bias gradient db[P] (+)= column sums of dY, through an fp32 [S][P]
-// workspace (S = wgrad_bias_slices); returns whether it was computed (16x16x32 kernel only)
-int wgrad_bias_slices(int M, int P, int Q);
-// wgrad_pp.hip: the ping-pong weight-gradient kernel (fp32 targets; wgrad() dispatches to it)
-bool wgrad_pp_supported(int M, int P, int Q, int S, int slice);
-void wgrad_pp(const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P, int Q, int S, int slice,
-              float* part, float* out, bool accumulate, float* bpart, int ctas, hipStream_t st);
-// hybrid form (no bias, more tiles than workgroups): whole tiles for the grid's whole rounds, slices for
-// the last one, finished by an ordered fix-up; part: wgrad_pp_hy_ws_floats floats
-bool wgrad_hy_plan(int M, int P, int Q, int ctas, int* full, int* rem, int* S, int* slice_kt);
-int64_t wgrad_pp_hy_ws_floats(int M, int P, int Q, int ctas);
-void wgrad_pp_hy(const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P, int Q, float* part,
-                 float* out, bool accumulate, int ctas, hipStream_t st);
 void wgrad_set_hy(int on);  // A/B: hybrid weight gradients where they apply
-// workspace floats wgrad() needs for this call (slice slabs or stream-K pieces)
-int64_t wgrad_ws_floats(int M, int P, int Q, bool out_f32, bool bias);
-// the kernel wgrad() runs for this call under the current settings: 0 / 1 gemm_wgrad.hip's kernel with
-// 16x16x32 / 32x32x16 MFMAs, 2 the ping-pong kernel, 3 its hybrid form
-int wgrad_arm(int M, int P, int Q, bool out_f32, bool bias);
-bool wgrad(const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P, int Q, float* part, void* out,
-           bool out_f32, bool accumulate, hipStream_t st, float* bpart = nullptr, void* bout = nullptr,
-           bool bout_f32 = false);
+// p = gemm_plan(gemm_settings(), gemm_cus(), a.M, a.N, a.K, epi, a.T)
+void gemm_tn(const GemmArgs& a, const GemmPlan& p, int epi, hipStream_t st);
+void gemm_tn_pp(const GemmArgs& a, const GemmPlan& p, int epi, hipStream_t st);  // gemm_pp.hip
+// gemm_wgrad.hip: dW[P,Q] (+)= dY[M,P]^T X[M,Q] under p = wgrad_plan(gemm_settings(), gemm_cus(), M, P, Q,
+// out_f32, bpart && bout); part: p.ws_floats fp32 workspace.  bpart / bout (optional): also the bias gradient
+// db[P] (+)= column sums of dY, through an fp32 [p.bias_rows][P] workspace; returns p.fused_bias, whether
+// it was computed
+bool wgrad(const WgradPlan& p, const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P, int Q,
+           float* part, void* out, bool out_f32, bool accumulate, hipStream_t st, float* bpart = nullptr,
+           void* bout = nullptr, bool bout_f32 = false);
+// wgrad_pp.hip: the ping-pong weight-gradient kernel (fp32 targets; arms 2 and 3 of wgrad()) and, on arm 3
+// (no bias, more tiles than workgroups: whole tiles for the grid's whole rounds, slices for the last one),
+// its ordered fix-up
+void wgrad_pp(const WgradPlan& p, const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P, int Q,
+              float* part, float* out, bool accumulate, float* bpart, hipStream_t st);
 
 // transpose.hip: desc int64 [n][6] = (src, dst, rows, cols, first tile, tiles per row band)
 int transpose_tiles(int R, int C);

@@ -31,7 +31,6 @@
 // Requires M % 64 == 0, P % 8 == 0, Q % 8 == 0, row strides % 8 == 0 (checked by the binding).
 #include <algorithm>
 
-#include "ab.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -432,45 +431,11 @@ __global__ __launch_bounds__(256) void wgrad_hy_reduce_kernel(const float* __res
 
 namespace pllm {
 
-// hybrid plan: with more tiles than workgroups, whole tiles for the whole rounds of the grid and the
-// remaining tiles as slices (>= 2 K-tiles each); false when it does not apply (no more tiles than
-// workgroups: wgrad_plan's uniform slices).  The remainder's slice count comes from wgrad_plan's cost model
-// (rounds x K-tiles per slice x ~2 us, plus the tile pieces written and read back at ~4 TB/s) instead of
-// "one round of slices" (ctas / rem): llama's gate/up projection (344 tiles on 256 CUs, 88 left) takes 5
-// slices in 2 rounds (1.4 tile times) instead of 2 slices in 1 round (1.5) (profiles/r6_wgrad_hy_cost.log)
-bool wgrad_hy_plan(int M, int P, int Q, int ctas, int* full, int* rem, int* S, int* slice_kt) {
-  const int kst = M / WBK;
-  const int ntiles = ((P + WT - 1) / WT) * ((Q + WT - 1) / WT);
-  if (M % WBK != 0 || kst < 2 || ctas <= 0 || ntiles <= ctas) return false;
-  *full = ntiles / ctas * ctas;
-  *rem = ntiles - *full;
-  int s = *rem > 0 ? std::max(1, std::min(ctas / *rem, kst / 2)) : 1;
-  if (*rem > 0 && ab_int("wgrad_hy_cost", 1)) {
-    double best_t = 1e30;
-    for (int c = 1; c <= 16 && (c == 1 || kst / c >= 8); ++c) {
-      const int per = (kst + c - 1) / c;
-      const int rounds = (*rem * c + ctas - 1) / ctas;
-      const double t = rounds * (double)per * 2.0e-6 + (c > 1 ? (double)*rem * c * WT * WT * 4.0 * 2 / 4.0e12 : 0.0);
-      if (t < best_t * 0.98) {
-        best_t = t;
-        s = c;
-      }
-    }
-  }
-  *slice_kt = (kst + s - 1) / s;
-  *S = *rem > 0 ? (kst + *slice_kt - 1) / *slice_kt : 0;
-  return true;
-}
+static_assert(WT == kPlanTile && WBK == kPlanKTile, "gemm_plan.h counts this kernel's tiles and K-tiles");
 
-int64_t wgrad_pp_hy_ws_floats(int M, int P, int Q, int ctas) {
-  int full, rem, S, skt;
-  return wgrad_hy_plan(M, P, Q, ctas, &full, &rem, &S, &skt) ? (int64_t)rem * S * WT * WT : 0;
-}
-
-void wgrad_pp_hy(const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P, int Q, float* part,
-                 float* out, bool accumulate, int ctas, hipStream_t st) {
-  int full, rem, S, skt;
-  if (!wgrad_hy_plan(M, P, Q, ctas, &full, &rem, &S, &skt)) return;
+void wgrad_pp(const WgradPlan& p, const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P, int Q,
+              float* part, float* out, bool accumulate, float* bpart, hipStream_t st) {
+  const bool hy = p.arm == 3;
   WPArgs g;
   g.A = (const uint16_t*)dy;
   g.B = (const uint16_t*)x;
@@ -479,53 +444,22 @@ void wgrad_pp_hy(const void* dy, int64_t lda, const void* x, int64_t ldb, int M,
   g.M = M;
   g.P = P;
   g.Q = Q;
-  g.S = 1;
-  g.slice_kt = skt;
-  g.part = part;
-  g.out = out;
-  g.accumulate = accumulate ? 1 : 0;
-  g.bpart = nullptr;
-  g.hy_full = full;
-  g.hy_rem = rem;
-  g.hy_s = S;
-  g.kst = M / WBK;
-  const int items = full + rem * S;
-  hipLaunchKernelGGL((wgrad_pp_kernel<false, true>), dim3(items < ctas ? items : ctas), dim3(WNT), 0, st, g);
-  if (rem > 0)
-    hipLaunchKernelGGL(wgrad_hy_reduce_kernel, dim3(rem, WT / 4), dim3(256), 0, st, part, out, P, Q,
-                       (Q + WT - 1) / WT, full, rem, S, g.accumulate);
-}
-
-bool wgrad_pp_supported(int M, int P, int Q, int S, int slice) {
-  (void)P;
-  (void)Q;
-  // >= 2 K-tiles per slice (the first K-tile is peeled), whole K-tiles
-  return M % WBK == 0 && slice % WBK == 0 && slice / WBK >= 2 && S >= 1;
-}
-
-void wgrad_pp(const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P, int Q, int S, int slice,
-              float* part, float* out, bool accumulate, float* bpart, int ctas, hipStream_t st) {
-  WPArgs g;
-  g.A = (const uint16_t*)dy;
-  g.B = (const uint16_t*)x;
-  g.lda = lda;
-  g.ldb = ldb;
-  g.M = M;
-  g.P = P;
-  g.Q = Q;
-  g.S = S;
-  g.slice_kt = slice / WBK;
+  g.S = hy ? 1 : p.S;
+  g.slice_kt = hy ? p.hy_slice_kt : p.slice / WBK;
   g.part = part;
   g.out = out;
   g.accumulate = accumulate ? 1 : 0;
   g.bpart = bpart;
-  g.hy_full = g.hy_rem = g.hy_s = 0;
+  g.hy_full = p.hy_full;  // zeros off the hybrid arm
+  g.hy_rem = p.hy_rem;
+  g.hy_s = p.hy_s;
   g.kst = M / WBK;
-  const int ntiles = ((P + WT - 1) / WT) * ((Q + WT - 1) / WT);
-  const int items = ntiles * S;
-  const int grid = items < ctas ? items : ctas;
-  if (bpart != nullptr) hipLaunchKernelGGL(wgrad_pp_kernel<true>, dim3(grid), dim3(WNT), 0, st, g);
-  else hipLaunchKernelGGL(wgrad_pp_kernel<false>, dim3(grid), dim3(WNT), 0, st, g);
+  if (hy) hipLaunchKernelGGL((wgrad_pp_kernel<false, true>), dim3(p.grid), dim3(WNT), 0, st, g);
+  else if (bpart != nullptr) hipLaunchKernelGGL(wgrad_pp_kernel<true>, dim3(p.grid), dim3(WNT), 0, st, g);
+  else hipLaunchKernelGGL(wgrad_pp_kernel<false>, dim3(p.grid), dim3(WNT), 0, st, g);
+  if (p.hy_rem > 0)
+    hipLaunchKernelGGL(wgrad_hy_reduce_kernel, dim3(p.hy_rem, WT / 4), dim3(256), 0, st, part, out, P, Q,
+                       (Q + WT - 1) / WT, p.hy_full, p.hy_rem, p.hy_s, g.accumulate);
 }
 
 }  // namespace pllm

@@ -288,6 +288,17 @@ def delta_model_outputs(B, T, N, K, chunked=False):
     return dict(do6=do, delta6=d.permute(0, 2, 1).contiguous())
 
 
+def expect_gemm_plan(M, N, K, epi, phased=4, T=0):
+    """The arm a case was written for, as ``gemm_plan`` reports it (without the grid): ping-pong kernel at K >= 128
+    (epilogue 6: and 16 | T), quadrant epilogues at K >= 2048 for epilogues 0, 2, 3, 4, 6; 4 (2) column-sum rows per
+    tile row with (without) them.  -> ([pp, quad], [tile rows, tile columns, column-sum rows])"""
+    pp = phased == 4 and K >= 128 and (epi != 6 or T % 16 == 0)
+    quad = pp and K >= 2048 and epi in (0, 2, 3, 4, 6)
+    tm, tn = -(-M // 256), -(-N // (128 if epi == 7 else 256))
+    groups = (4 if phased == 4 and K >= 2048 else 2) * tm
+    return [int(pp), int(quad)], [tm, tn, groups]
+
+
 # ------------------------------------------------------------------------------------------------ wgrad
 # name -> (M, P, Q, S, slice, grid8) and, for grid8 cases (persistent grid cut to 8 workgroups), the hybrid plan
 # (full, rem, S, K-tiles per slice).  S / slice are what wgrad_plan's cost model gives today; the GPU tests assert
@@ -304,6 +315,23 @@ WGRAD_CASES = {
     "hybrid_rem0": (256, 776, 776, 1, 256, True),   # 16 tiles on 8 workgroups: two whole rounds, nothing sliced
 }
 WGRAD_HYBRID = {"hybrid": (8, 4, 2, 8), "hybrid_rem0": (16, 0, 0, 4)}
+
+
+def wgrad_arm(name, mf, out_f32, bias):
+    """0 / 1: the one-barrier kernel (16x16x32 / 32x32x16); 2: ping-pong (fp32 targets, >= 2 K-tiles per slice);
+    3: hybrid (fp32 target, no bias, more tiles than workgroups)."""
+    slice_rows, grid8 = WGRAD_CASES[name][4:]
+    if mf:
+        return 0 if mf == 16 else 1
+    if not out_f32 or slice_rows < 128:
+        return 0
+    return 3 if grid8 and not bias else 2
+
+
+def expect_wgrad_plan(name, mf, out_f32, bias):
+    """What ``wgrad_plan`` reports for a WGRAD_CASES row under ``wgrad_set_mfma(mf)``."""
+    arm = wgrad_arm(name, mf, out_f32, bias)
+    return [arm, *WGRAD_CASES[name][3:5]] + (list(WGRAD_HYBRID[name]) if arm == 3 else [0, 0, 0, 0])
 
 
 @functools.lru_cache(maxsize=None)

@@ -69,14 +69,10 @@ def _poison(rows, cols):
 
 
 def _expect_plan(M, N, K, epi, phased=4, T=0, grid=None):
-    """The arm a case was written for: ping-pong kernel at K >= 128 (epilogue 6: and 16 | T), quadrant epilogues
-    at K >= 2048 for epilogues 0, 2, 3, 4, 6; 4 (2) column-sum rows per tile row with (without) them."""
-    pp = phased == 4 and K >= 128 and (epi != 6 or T % 16 == 0)
-    quad = pp and K >= 2048 and epi in (0, 2, 3, 4, 6)
-    tm, tn = -(-M // 256), -(-N // (128 if epi == 7 else 256))
+    """The arm a case was written for (``_gemm_refs.expect_gemm_plan``), asserted on the op's plan."""
+    head, tail = G.expect_gemm_plan(M, N, K, epi, phased, T)
     plan = list(_ops().gemm_plan(M, N, K, epi, T))
-    groups = (4 if phased == 4 and K >= 2048 else 2) * tm
-    assert plan[:2] == [int(pp), int(quad)] and plan[3:] == [tm, tn, groups], (plan, (M, N, K, epi))
+    assert plan[:2] == head and plan[3:] == tail, (plan, (M, N, K, epi))
     if grid is not None:
         assert plan[2] == grid, plan
     return plan
@@ -212,17 +208,6 @@ def _sentinel_view(t, dtype):
     return buf, v
 
 
-def _wgrad_arm(name, mf, out_f32, bias):
-    """0 / 1: the one-barrier kernel (16x16x32 / 32x32x16); 2: ping-pong (fp32 targets, >= 2 K-tiles per slice);
-    3: hybrid (fp32 target, no bias, more tiles than workgroups)."""
-    slice_rows, grid8 = G.WGRAD_CASES[name][4:]
-    if mf:
-        return 0 if mf == 16 else 1
-    if not out_f32 or slice_rows < 128:
-        return 0
-    return 3 if grid8 and not bias else 2
-
-
 @pytest.mark.parametrize("name", list(G.WGRAD_CASES))
 def test_wgrad_edges(name):
     """Fresh bf16 output, bf16 and fp32 accumulation (the target a view between sentinels), the fused bias
@@ -237,9 +222,7 @@ def test_wgrad_edges(name):
                 for of32 in (False, True):
                     for bias in (False, True):
                         plan = list(_ops().wgrad_plan(M, P, Q, of32, bias))
-                        arm = _wgrad_arm(name, mf, of32, bias)
-                        hy = list(G.WGRAD_HYBRID[name]) if arm == 3 else [0, 0, 0, 0]
-                        assert plan == [arm, S_, slice_rows] + hy, (plan, mf, of32, bias)
+                        assert plan == G.expect_wgrad_plan(name, mf, of32, bias), (plan, mf, of32, bias)
 
                 def run():
                     out = dict(fresh=_ops().wgrad(dy, x))

@@ -38,7 +38,7 @@ SHAPES = [(512, 768, 768), (300, 520, 128), (1024, 3072, 768), (777, 264, 192), 
 
 
 # phased 4 = the ping-pong kernel (csrc/gemm_pp.hip; its MFMA shape is fixed, mf is ignored),
-# the default (csrc/gemm.hip g_gemm_phased); 0 / 2 = the round-3 kernel kept for A/B
+# the default (csrc/gemm_plan.h GemmSettings::phased); 0 / 2 = the round-3 kernel kept for A/B
 DEFAULT_KERNEL = 4
 KERNELS = [(16, 0), (32, 0), (16, 2), (32, 2), (16, 4)]
 
