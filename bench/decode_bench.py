@@ -6,9 +6,11 @@ token (``DecodeGraph``).  Also times the decode-attention kernel alone against t
 forward kernel run with a single query row (what decode used before the split-KV kernel), and
 with a sliding window (``attn_decode(window=)``: S = 8192 cached keys, D = 128, B in {1, 64}, window 0
 and 1024, interleaved round by round).  ``--kernels-only`` stops after the kernel arms.
+``--softcap C`` runs every batch size twice, without and with final-logit soft-capping (``final_logit_softcap=C``:
+elementwise ops on the step's [B, V] logits).  ``--model-only`` skips the kernel arms.
 Prints one JSON line per configuration.
 
-usage: python bench/decode_bench.py [--batches 1,16,64] [--prompt 128] [--new 256] [--kernels-only]
+usage: python bench/decode_bench.py [--batches 1,16,64] [--prompt 128] [--new 256] [--kernels-only] [--softcap 30]
 """
 from __future__ import annotations
 
@@ -43,6 +45,8 @@ def main():
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--softcap", type=float, default=None)
+    ap.add_argument("--model-only", action="store_true")
     args = ap.parse_args()
     import torch
     from pretraining_llm_amd import ops
@@ -51,7 +55,7 @@ def main():
     dev = torch.device("cuda:0")
 
     # kernel-level: split-KV decode vs flash forward with one query row
-    for B, S in ((1, 1024), (16, 1024), (64, 1024), (8, 4096)):
+    for B, S in () if args.model_only else ((1, 1024), (16, 1024), (64, 1024), (8, 4096)):
         H, D = 12, 64
         q = torch.randn(B, 1, H, D, device=dev, dtype=torch.bfloat16)
         k = torch.randn(B, S, H, D, device=dev, dtype=torch.bfloat16)
@@ -66,7 +70,7 @@ def main():
 
     # sliding window: a local layer reads the last `window` rows of the count instead of all S
     import statistics
-    for B in (1, 64):
+    for B in () if args.model_only else (1, 64):
         S, H, Hkv, D = 8192, 16, 16, 128
         q = torch.randn(B, 1, H, D, device=dev, dtype=torch.bfloat16)
         k = torch.randn(B, S, Hkv, D, device=dev, dtype=torch.bfloat16)
@@ -93,9 +97,13 @@ def main():
     torch.manual_seed(0)
     cfg = get_preset(args.model)
     model = GPT(cfg).to(dev, torch.bfloat16).eval()
-    for B in (int(b) for b in args.batches.split(",")):
+    caps = [None] + ([args.softcap] if args.softcap else [])
+    for B, cap in ((int(b), c) for b in args.batches.split(",") for c in caps):
         idx = torch.randint(0, cfg.vocab_size, (B, args.prompt), device=dev)
         res = {"model": args.model, "batch": B, "prompt": args.prompt, "new_tokens": args.new}
+        if args.softcap:
+            model.config = cfg.replace(final_logit_softcap=cap)  # no parameters: the same weights
+            res["final_logit_softcap"] = cap
         for mode in ("eager", "graph"):
             g = mode == "graph"
             model.generate(idx, 4, temperature=0.0, cuda_graph=g)  # warm-up (library init, graph pools)

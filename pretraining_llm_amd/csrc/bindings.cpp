@@ -4,6 +4,7 @@
 // (a wrong shape must fail here, never fault on the GPU) and launches on the
 // current HIP stream, so the ops compose with torch streams and hipGraph capture.
 #include <ATen/ATen.h>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <c10/hip/HIPStream.h>
@@ -703,6 +704,48 @@ Tensor cross_entropy(const Tensor& logits, const Tensor& targets, const std::opt
   return loss;
 }
 
+// the same with z-loss and final-logit soft-capping inside the kernel (see cross_entropy.hip); the returned
+// per-row loss includes the z term.  ``lse``: optional fp32 [N] output, the rows' log-sum-exp of the capped logits.
+Tensor cross_entropy_aux(const Tensor& logits, const Tensor& targets, const std::optional<Tensor>& dlogits,
+                         int64_t ignore_index, const std::optional<Tensor>& inv_n_opt, double z_loss, double softcap,
+                         const std::optional<Tensor>& lse) {
+  check_bf16(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [N, V] with unit column stride");
+  const int64_t N = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(logits.stride(0) % 8 == 0 && V % 8 == 0, "cross_entropy_aux: V and row stride must be multiples of 8");
+  TORCH_CHECK(V <= pllm::cross_entropy_max_vocab(),
+              "cross_entropy_aux: vocab too large for the register-resident kernel");
+  TORCH_CHECK(z_loss >= 0.0 && std::isfinite(z_loss), "cross_entropy_aux: z_loss must be >= 0, got ", z_loss);
+  TORCH_CHECK(softcap >= 0.0 && std::isfinite(softcap), "cross_entropy_aux: softcap must be >= 0 (0: off), got ",
+              softcap);
+  check_aligned16(logits, "logits");
+  TORCH_CHECK(targets.is_cuda() && targets.numel() == N, "targets shape");
+  Tensor tg = targets.reshape({N}).to(at::kLong).contiguous();
+  if (dlogits) {
+    check_bf16(*dlogits, "dlogits");
+    TORCH_CHECK(dlogits->sizes() == logits.sizes() && dlogits->strides() == logits.strides(), "dlogits layout");
+  }
+  if (lse)
+    TORCH_CHECK(lse->is_cuda() && lse->scalar_type() == at::kFloat && lse->dim() == 1 && lse->size(0) == N &&
+                    lse->is_contiguous(),
+                "cross_entropy_aux: lse must be a contiguous [N] fp32 device tensor");
+  Tensor loss = at::empty({N}, logits.options().dtype(at::kFloat));
+  Tensor inv_n;
+  if (inv_n_opt) {
+    TORCH_CHECK(inv_n_opt->is_cuda() && inv_n_opt->scalar_type() == at::kFloat && inv_n_opt->numel() == 1,
+                "cross_entropy_aux: inv_n must be a 1-element fp32 device tensor");
+    inv_n = inv_n_opt->reshape({1});
+  } else {
+    inv_n = (tg != ignore_index).sum().to(at::kFloat).clamp_min(1.0).reciprocal().reshape({1});
+  }
+  if (N)
+    pllm::cross_entropy_aux(logits.data_ptr(), logits.stride(0), tg.data_ptr<int64_t>(), (int)N, (int)V,
+                            (int)ignore_index, loss.data_ptr<float>(), dlogits ? dlogits->data_ptr() : nullptr,
+                            inv_n.data_ptr<float>(), (float)z_loss, (float)softcap,
+                            lse ? lse->data_ptr<float>() : nullptr, cur_stream());
+  return loss;
+}
+
 // ---------------------------------------------------------------- optimizer
 void adamw_(Tensor& param, Tensor& master, Tensor& m, Tensor& v, const Tensor& grad, double lr, double b1, double b2,
             double eps, double wd, int64_t step, double grad_scale, const std::optional<Tensor>& scale,
@@ -1246,6 +1289,8 @@ TORCH_LIBRARY(pllm, m) {
   m.def("zero_ranges_(Tensor(a!) buf, Tensor ranges, int total_len) -> ()");
   m.def("cross_entropy_max_vocab() -> int", []() { return (int64_t)pllm::cross_entropy_max_vocab(); });
   m.def("cross_entropy(Tensor logits, Tensor targets, Tensor(a!)? dlogits, int ignore_index, Tensor? inv_n=None) -> Tensor");
+  m.def("cross_entropy_aux(Tensor logits, Tensor targets, Tensor(a!)? dlogits, int ignore_index, Tensor? inv_n, "
+        "float z_loss, float softcap, Tensor(b!)? lse) -> Tensor");
   m.def("adamw_(Tensor(a!) param, Tensor(b!) master, Tensor(c!) m, Tensor(d!) v, Tensor grad, float lr, float b1, float b2, float eps, float wd, int step, float grad_scale, Tensor? scale, Tensor? wd_mask, Tensor? hyper=None) -> ()");
   m.def("sumsq(Tensor x) -> Tensor");
   m.def("grad_norm_clip(Tensor x, float grad_scale, float max_norm) -> Tensor");
@@ -1281,6 +1326,7 @@ TORCH_LIBRARY_IMPL(pllm, CUDA, m) {
   m.impl("lse_merge_", lse_merge_);
   m.impl("zero_ranges_", zero_ranges_);
   m.impl("cross_entropy", cross_entropy);
+  m.impl("cross_entropy_aux", cross_entropy_aux);
   m.impl("adamw_", adamw_);
   m.impl("sumsq", sumsq);
   m.impl("grad_norm_clip", grad_norm_clip);

@@ -110,6 +110,11 @@ void qk_norm_bwd(void* dqkv, const void* qkv, const float* rstd, const void* wq,
 // cross_entropy.hip
 void cross_entropy(const void* logits, int64_t ld, const int64_t* targets, int N, int V, int ignore_index,
                    float* loss, void* dlogits, const float* inv_n, hipStream_t st);
+// the same with an auxiliary z-loss (loss += z_loss * lse^2) and final-logit soft-capping (softcap * tanh(x / softcap),
+// 0: off); lse (optional): fp32 [N], the rows' log-sum-exp (0 on ignored rows)
+void cross_entropy_aux(const void* logits, int64_t ld, const int64_t* targets, int N, int V, int ignore_index,
+                       float* loss, void* dlogits, const float* inv_n, float z_loss, float softcap, float* lse,
+                       hipStream_t st);
 int cross_entropy_max_vocab();
 
 // adamw.hip

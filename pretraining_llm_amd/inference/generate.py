@@ -61,7 +61,7 @@ def forward_cached(model, idx: torch.Tensor, cache: KVCache, pos: int,
     else:
         xl, rl = x[:, -1:], (res[:, -1:] if res is not None else None)
     logits, _ = model.layer_norm.linear(xl, rl, model.head_weight, model.head_bias)
-    return logits[:, -1, :].float()
+    return ops.softcap(logits[:, -1, :].float(), cfg.final_logit_softcap)
 
 
 @torch.no_grad()
@@ -79,7 +79,8 @@ def forward_decode(model, tok: torch.Tensor, cache: KVCache, pos_t: torch.Tensor
     for i, blk in enumerate(model.attn_blocks):
         x, res = blk.forward_decode(x, res, cache, i, pos_t, len_t, rope)
     logits, _ = model.layer_norm.linear(x, res, model.head_weight, model.head_bias)
-    return logits[:, -1, :].float()
+    # (final-logit soft-capping: elementwise torch ops on [B, V], captured with the rest of the step)
+    return ops.softcap(logits[:, -1, :].float(), cfg.final_logit_softcap)
 
 
 class DecodeGraph:

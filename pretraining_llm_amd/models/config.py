@@ -56,6 +56,13 @@ class ModelConfig:
     # positions are unchanged; with doc_mask a local layer sees the intersection of window and document
     sliding_window: Optional[int] = None
     sliding_window_pattern: int = 0
+    # Auxiliary z-loss (PaLM / OLMo-2 / Chameleon): z_loss * logsumexp(logits)^2 per token added to the TRAINING loss
+    # (it keeps the softmax normaliser from drifting); model.eval() losses and Trainer.evaluate stay plain CE.
+    # Final-logit soft-capping (Gemma-2): logits -> cap * tanh(logits / cap) before the softmax (None: off).
+    # Architecture: it applies to the loss in both modes and to every logits tensor the model or generation hands out.
+    # Both run inside the fused CE kernel; no parameters
+    z_loss: float = 0.0
+    final_logit_softcap: Optional[float] = None
     init: str = "gpt2"                      # gpt2 | torch_default
     init_std: float = 0.02
     # True / False, a float fraction of the blocks, or "auto": checkpoint only as many blocks as
@@ -81,6 +88,10 @@ class ModelConfig:
                              "(every n-th layer global)")
         if self.sliding_window_pattern and self.sliding_window is None:
             raise ValueError(f"sliding_window_pattern={self.sliding_window_pattern} needs a sliding_window")
+        if self.z_loss is None or not self.z_loss >= 0:
+            raise ValueError(f"z_loss={self.z_loss}: the coefficient is >= 0 (0: off)")
+        if self.final_logit_softcap is not None and not self.final_logit_softcap > 0:
+            raise ValueError(f"final_logit_softcap={self.final_logit_softcap}: the cap is > 0 (None: off)")
         if self.ffn_hidden is None:
             if self.mlp == "swiglu":
                 h = int(2 * (4 * self.n_embed) / 3)
@@ -220,6 +231,12 @@ PRESETS = {
                                         ffn_hidden=5504, qk_norm=True),
     "llama-tiny-qknorm": lambda: _llama(vocab_size=512, context_length=128, n_embed=128, n_head=4, n_blocks=2,
                                         n_kv_head=2, ffn_hidden=256, qk_norm=True),
+    # the same two with the auxiliary z-loss next to QK-norm (OLMo-2); the tiny one also soft-caps its final logits
+    "llama-1.3b-zloss": lambda: _llama(vocab_size=50304, context_length=2048, n_embed=2048, n_head=16, n_blocks=24,
+                                       ffn_hidden=5504, qk_norm=True, z_loss=1e-4),
+    "llama-tiny-zloss": lambda: _llama(vocab_size=512, context_length=128, n_embed=128, n_head=4, n_blocks=2,
+                                       n_kv_head=2, ffn_hidden=256, qk_norm=True, z_loss=1e-4,
+                                       final_logit_softcap=30.0),
 }
 
 

@@ -349,6 +349,9 @@ class GPT(nn.Module):
             from .compat import install_ref_state_dict_hooks
             install_ref_state_dict_hooks(self)
         self._rope = None
+        # the last training forward's z term (config.z_loss times the valid tokens' mean logsumexp^2), 1-element fp32
+        # on the loss's device; written with copy_ so that a replayed hipGraph refreshes it.  Not a registered buffer
+        self.z_term = None
         self.parallel = None  # ParallelGroups once parallel.model_parallel.parallelize_gpt ran
         self.reset_parameters()
 
@@ -543,15 +546,26 @@ class GPT(nn.Module):
             from ..parallel.tensor import _split_dim
             targets = _split_dim(targets, 1, pg.tp_group)
         B, T, C = h.shape
+        cap = self.config.final_logit_softcap
         if targets is None:
             logits = ops.linear(h, self.head_weight, self.head_bias)
-            return logits, None
+            return ops.softcap(logits, cap), None
+        # the z-loss is a training regulariser: eval-mode losses stay plain CE (of the capped logits)
+        z = self.config.z_loss if self.training else 0.0
+        kw = {}
+        if z or cap is not None:  # (both off: the calls are the ones without the options)
+            kw = dict(z_loss=z, softcap=cap, z_out=self._z_term_buf(h.device) if z else None)
         if not return_logits:
             # training hot path: LM head GEMM + fused CE that overwrites the logits with dlogits
-            return None, ops.lm_head_cross_entropy(h, self.head_weight, self.head_bias, targets)
+            return None, ops.lm_head_cross_entropy(h, self.head_weight, self.head_bias, targets, **kw)
         logits = ops.linear(h.reshape(B * T, C), self.head_weight, self.head_bias)
-        loss = ops.cross_entropy(logits, targets.reshape(B * T))
-        return logits.view(B, T, -1), loss
+        loss = ops.cross_entropy(logits, targets.reshape(B * T), **kw)  # caps inside; the logits handed out below
+        return ops.softcap(logits, cap).view(B, T, -1), loss
+
+    def _z_term_buf(self, device):
+        if self.z_term is None or self.z_term.device != device:
+            self.z_term = torch.zeros(1, dtype=torch.float32, device=device)
+        return self.z_term
 
     def forward_embedding(self, idx):
         """(hidden, residual) of the LAST block: hidden = act(mlp.hidden(ln2(res))) [B,T,F],

@@ -1241,9 +1241,23 @@ def _logits_into(ws, hc, weight, bias):
     return lg
 
 
+def _ce_rows(lg, targets, dlogits, ignore_index, inv_n, z_loss, cap, lse):
+    """Per-row losses of one block of logits: the plain kernel with both options off, else cross_entropy_aux
+    (z term included; ``lse``: the rows of the log-sum-exp buffer to fill, or None)."""
+    if not z_loss and not cap:
+        return _ops().cross_entropy(lg, targets, dlogits, ignore_index, inv_n)
+    return _ops().cross_entropy_aux(lg, targets, dlogits, ignore_index, inv_n, float(z_loss), float(cap or 0.0), lse)
+
+
+def _z_term(lse, z_loss, inv_n, z_out):
+    """z_loss * mean over the valid rows of lse^2 (ignored rows hold 0) into the 1-element ``z_out``."""
+    if z_out is not None and lse is not None:
+        z_out.copy_((lse.square().sum() * inv_n * z_loss).reshape(1))
+
+
 class _LMHeadCEFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, h, weight, bias, targets, ignore_index):
+    def forward(ctx, h, weight, bias, targets, ignore_index, z_loss=0.0, cap=None, z_out=None):
         N, C = h.shape
         V = weight.shape[0]
         n_valid = (targets != ignore_index).sum().clamp_min(1)
@@ -1269,12 +1283,14 @@ class _LMHeadCEFn(torch.autograd.Function):
               torch.empty(V, C, dtype=torch.float32, device=h.device)) if need_w else None
         db = torch.zeros(V, dtype=torch.float32, device=h.device) if need_b else None
         rows = torch.empty(N, dtype=torch.float32, device=h.device)
+        lse = torch.empty(N, dtype=torch.float32, device=h.device) if (z_loss or cap) else None
         wt = _shadow(weight)
         for r0 in range(0, N, R):
             r1 = min(N, r0 + R)
             hc = h[r0:r1]
             lg = _logits_into(ws, hc, weight, bias)
-            rows[r0:r1] = _ops().cross_entropy(lg, targets[r0:r1], lg, ignore_index, inv_n)
+            rows[r0:r1] = _ce_rows(lg, targets[r0:r1], lg, ignore_index, inv_n, z_loss, cap,
+                                   None if lse is None else lse[r0:r1])
             if need_h:  # dh = dlogits @ W (through the W^T shadow when present, see _dgrad)
                 torch.mm(lg, wt.t() if wt is not None else weight, out=dh[r0:r1])
             if need_w:
@@ -1285,6 +1301,8 @@ class _LMHeadCEFn(torch.autograd.Function):
         ctx.save_for_backward(dh, None if ctx.direct else dw, db)
         ctx.w, ctx.b = weight, bias
         ctx.wdtype = weight.dtype
+        if z_loss:
+            _z_term(lse, z_loss, inv_n[0], z_out)
         return rows.sum() * inv_n[0]
 
     @staticmethod
@@ -1321,37 +1339,71 @@ class _LMHeadCEFn(torch.autograd.Function):
             else:
                 gb = db.mul_(g).to(ctx.wdtype)
         ctx.w = ctx.b = None
-        return gh, gw, gb, None, None
+        return gh, gw, gb, None, None, None, None, None
 
 
-def lm_head_cross_entropy(h, weight, bias, targets, ignore_index: int = -100):
+def _check_ce_options(z_loss, softcap):
+    if not z_loss >= 0:
+        raise ValueError(f"z_loss={z_loss}: must be >= 0")
+    if softcap is not None and not softcap > 0:
+        raise ValueError(f"softcap={softcap}: must be > 0 (None: off)")
+
+
+def softcap(logits, cap: Optional[float]):
+    """Final-logit soft-capping ``cap * tanh(logits / cap)`` of a logits tensor that is handed out (``cap`` None:
+    the tensor itself).  Plain elementwise torch ops of fixed shape, so it captures into the decode hipGraph; tanh is
+    monotone, so greedy decoding does not change."""
+    return ref.softcap(logits, cap)
+
+
+def lm_head_cross_entropy(h, weight, bias, targets, ignore_index: int = -100, z_loss: float = 0.0,
+                          softcap: Optional[float] = None, z_out=None):
     """mean CE of ``h @ weight^T + bias`` against ``targets`` without returning logits
-    (chunked over rows on the HIP path: no [N, V] buffer in training or evaluation)."""
+    (chunked over rows on the HIP path: no [N, V] buffer in training or evaluation).
+    ``softcap``: the logits pass through ``softcap * tanh(. / softcap)`` first; ``z_loss``: adds
+    ``z_loss * logsumexp(logits)^2`` per token, both inside the CE kernel; ``z_out``: a 1-element fp32 tensor that
+    receives the z term of the returned loss."""
+    _check_ce_options(z_loss, softcap)
     targets = targets.reshape(-1)
     h = h.reshape(-1, h.shape[-1])
     if _hip_op("ce", h) and torch.is_grad_enabled() and (h.requires_grad or weight.requires_grad):
-        return _LMHeadCEFn.apply(h, weight, bias, targets, ignore_index)
+        if not z_loss and softcap is None:
+            return _LMHeadCEFn.apply(h, weight, bias, targets, ignore_index)
+        return _LMHeadCEFn.apply(h, weight, bias, targets, ignore_index, z_loss, softcap, z_out)
     if _hip_op("ce", h):
         N, V = h.shape[0], weight.shape[0]
         R = _ce_chunk_rows(N, V, _ce_budget_bytes(h.device))
         ws = torch.empty(R, V, dtype=h.dtype, device=h.device)
         rows = torch.empty(N, dtype=torch.float32, device=h.device)
+        lse = torch.empty(N, dtype=torch.float32, device=h.device) if z_loss and z_out is not None else None
         for r0 in range(0, N, R):
             r1 = min(N, r0 + R)
             lg = _logits_into(ws, h[r0:r1], weight, bias)
-            rows[r0:r1] = _ops().cross_entropy(lg, targets[r0:r1], None, ignore_index)
-        return rows.sum() / (targets != ignore_index).sum().clamp_min(1)
+            rows[r0:r1] = _ce_rows(lg, targets[r0:r1], None, ignore_index, None, z_loss, softcap,
+                                   None if lse is None else lse[r0:r1])
+        n_valid = (targets != ignore_index).sum().clamp_min(1)
+        _z_term(lse, z_loss, n_valid.to(torch.float32).reciprocal(), z_out)
+        return rows.sum() / n_valid
     logits = F.linear(h, weight, bias)
-    return cross_entropy(logits, targets, ignore_index)
+    return cross_entropy(logits, targets, ignore_index, z_loss, softcap, z_out)
 
 
-def cross_entropy(logits, targets, ignore_index: int = -100):
-    """Mean token cross-entropy over ``logits [N, V]`` (no in-place tricks)."""
+def cross_entropy(logits, targets, ignore_index: int = -100, z_loss: float = 0.0, softcap: Optional[float] = None,
+                  z_out=None):
+    """Mean token cross-entropy over ``logits [N, V]`` (no in-place tricks); ``z_loss`` / ``softcap`` / ``z_out`` as
+    in lm_head_cross_entropy."""
+    _check_ce_options(z_loss, softcap)
     targets = targets.reshape(-1)
     if _hip(logits) and not (torch.is_grad_enabled() and logits.requires_grad):
-        rows = _ops().cross_entropy(logits.contiguous(), targets, None, ignore_index)
-        return rows.sum() / (targets != ignore_index).sum().clamp_min(1)
-    return ref.cross_entropy(logits, targets, ignore_index)
+        lse = torch.empty(targets.shape[0], dtype=torch.float32, device=logits.device) \
+            if z_loss and z_out is not None else None
+        rows = _ce_rows(logits.contiguous(), targets, None, ignore_index, None, z_loss, softcap, lse)
+        n_valid = (targets != ignore_index).sum().clamp_min(1)
+        _z_term(lse, z_loss, n_valid.to(torch.float32).reciprocal(), z_out)
+        return rows.sum() / n_valid
+    if not z_loss and softcap is None:
+        return ref.cross_entropy(logits, targets, ignore_index)
+    return ref.cross_entropy(logits, targets, ignore_index, z_loss, softcap, z_out)
 
 
 # ---------------------------------------------------------------------------

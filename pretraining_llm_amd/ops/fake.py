@@ -130,6 +130,10 @@ def register() -> None:
     def _(logits, targets, dlogits, ignore_index, inv_n=None):
         return logits.new_empty((logits.shape[0],), dtype=f32)
 
+    @_reg("cross_entropy_aux")
+    def _(logits, targets, dlogits, ignore_index, inv_n, z_loss, softcap, lse):
+        return logits.new_empty((logits.shape[0],), dtype=f32)
+
     @_reg("adamw_")
     def _(param, master, m, v, grad, lr, b1, b2, eps, wd, step, grad_scale, scale, wd_mask, hyper=None):
         return None

@@ -143,8 +143,27 @@ def rope(x, cos, sin):
     return out.to(x.dtype)
 
 
-def cross_entropy(logits, targets, ignore_index: int = -100):
-    return F.cross_entropy(logits.float(), targets.long(), ignore_index=ignore_index)
+def softcap(logits, cap):
+    """``cap * tanh(logits / cap)`` in fp32, returned in the input's dtype (``cap`` None: unchanged)."""
+    if cap is None:
+        return logits
+    return (torch.tanh(logits.float() / cap) * cap).to(logits.dtype)
+
+
+def cross_entropy(logits, targets, ignore_index: int = -100, z_loss: float = 0.0, softcap=None, z_out=None):
+    """Mean CE of ``softcap * tanh(logits / softcap)`` plus ``z_loss * logsumexp^2`` averaged over the valid rows.
+    ``z_out``: a 1-element fp32 tensor that receives the z term (the second summand) without a graph."""
+    y = logits.float()
+    if softcap is not None:
+        y = torch.tanh(y / softcap) * softcap  # fp32, not rounded back to the logits' dtype
+    loss = F.cross_entropy(y, targets.long(), ignore_index=ignore_index)
+    if z_loss:
+        valid = (targets != ignore_index).to(y.dtype)
+        zt = z_loss * (torch.logsumexp(y, -1).square() * valid).sum() / valid.sum().clamp_min(1)
+        if z_out is not None:
+            z_out.copy_(zt.detach().reshape(1))
+        loss = loss + zt
+    return loss
 
 
 def embedding(idx, wte, wpe=None, pos_offset: int = 0):

@@ -44,7 +44,8 @@ def model_config_from(cfg: dict) -> ModelConfig:
     preset = cfg.get("model_preset")
     dims = {k: cfg[k] for k in ("vocab_size", "context_length", "n_embed", "n_head", "n_blocks") if k in cfg}
     extra = {k: cfg[k] for k in ("n_kv_head", "ffn_hidden", "activation_checkpointing", "qk_norm", "qk_norm_eps",
-                                  "doc_mask", "doc_sep_token", "sliding_window", "sliding_window_pattern")
+                                  "doc_mask", "doc_sep_token", "sliding_window", "sliding_window_pattern", "z_loss",
+                                  "final_logit_softcap")
              if cfg.get(k) is not None}
     if preset:
         mc = get_preset(preset)
@@ -346,6 +347,9 @@ class Trainer:
                        "peak_mem_gb": peak_memory_gb(self.device)}
                 if self.opt.last_grad_norm is not None:
                     rec["grad_norm"] = float(self.opt.last_grad_norm)
+                if self.mcfg.z_loss > 0 and self.model.z_term is not None:
+                    # the z term of this step's last forward (train_loss is the total: train_loss - z_loss is the CE)
+                    rec["z_loss"] = float(all_reduce_mean(self.model.z_term[0].clone()))
                 if self.di.is_master:
                     self.log(f"Step {step}: Train Loss={tl:.4f}, Val Loss={last_val:.4f}, LR={self.opt.lr:.2e}, "
                              f"Time={dt * 1000:.2f}ms, tok/s={tps:,.0f}, MFU={rec['mfu'] * 100:.1f}%")
