@@ -3,7 +3,12 @@
 attention) on the same random data, interleaved rounds in one process.
 
 Reports TFLOP/s with causal FLOPs counted as half of dense: fwd 2*2*B*H*T*T*D/2,
-bwd 2.5x fwd (5 GEMM-shaped products)."""
+bwd 2.5x fwd (5 GEMM-shaped products).
+
+``--sinks``: attention sinks on against off on the same data, the arms alternating round by round after a warm-up
+round, with the off arm run twice per round (``off`` / ``off2``: the spread of one identical side against itself):
+the forward with ``sinks=``, the backward plus ``attn_sink_bwd`` (delta kept through ``delta_out``), and
+``attn_sink_bwd`` alone.  Medians over the rounds in us."""
 import argparse
 import json
 import math
@@ -36,6 +41,7 @@ def main():
     ap.add_argument("--only", default="", help="fwd|bwd: run only our kernel (for profiling)")
     ap.add_argument("--rope-ab", action="store_true", help="our fwd/bwd without RoPE vs with the rope_qk pre-pass + rotate-back backward")
     ap.add_argument("--ours", action="store_true", help="time only the HIP kernels (fwd_us / bwd_us), no SDPA")
+    ap.add_argument("--sinks", action="store_true", help="attention sinks on vs off, alternating arms")
     args = ap.parse_args()
     from pretraining_llm_amd.ops import _lib
     _lib.require()
@@ -52,6 +58,35 @@ def main():
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         ours_f = lambda: torch.ops.pllm.attn_fwd(q, k, v, True, scale)
         ours_b = lambda: torch.ops.pllm.attn_bwd(do, q, k, v, o, lse, dq, dk, dv, True, scale)
+        if args.sinks:
+            import statistics
+            sinks = torch.randn(H, device=dev).to(torch.bfloat16)
+            o_s, lse_s = torch.ops.pllm.attn_fwd(q, k, v, True, scale, None, sinks)
+            delta = torch.empty_like(lse_s)
+            slot = torch.zeros(H, device=dev)
+
+            def bwd_on():
+                torch.ops.pllm.attn_bwd(do, q, k, v, o_s, lse_s, dq, dk, dv, True, scale, None, None, None, None, None,
+                                        delta)
+                torch.ops.pllm.attn_sink_bwd(lse_s, delta, sinks, slot, True)
+            bwd_on()
+            arms = {"fwd_off": ours_f, "fwd_on": lambda: torch.ops.pllm.attn_fwd(q, k, v, True, scale, None, sinks),
+                    "fwd_off2": ours_f, "bwd_off": ours_b, "bwd_on": bwd_on, "bwd_off2": ours_b,
+                    "sink_bwd": lambda: torch.ops.pllm.attn_sink_bwd(lse_s, delta, sinks, slot, True)}
+            times = {n: [] for n in arms}
+            for rnd in range(args.rounds + 1):
+                for n, fn in arms.items():
+                    t = 1e6 * timeit(fn, iters=20)
+                    if rnd > 0:  # round 0 is warm-up
+                        times[n].append(t)
+            med = {n: statistics.median(ts) for n, ts in times.items()}
+            res = {"cfg": cfg, "rounds": args.rounds, **{n + "_us": round(m, 2) for n, m in med.items()},
+                   **{n + "_min_max_us": [round(min(ts), 2), round(max(ts), 2)] for n, ts in times.items()}}
+            for p in ("fwd", "bwd"):
+                res[p + "_on_minus_off_us"] = round(med[p + "_on"] - med[p + "_off"], 2)
+                res[p + "_off2_minus_off_us"] = round(med[p + "_off2"] - med[p + "_off"], 2)
+            print(json.dumps(res), flush=True)
+            continue
         if args.rope_ab:
             from pretraining_llm_amd import ops
             cos, sin = ops.rope_cache(T, D, 10000.0, dev)

@@ -7,7 +7,9 @@ forward kernel run with a single query row (what decode used before the split-KV
 with a sliding window (``attn_decode(window=)``: S = 8192 cached keys, D = 128, B in {1, 64}, window 0
 and 1024, interleaved round by round).  ``--kernels-only`` stops after the kernel arms.
 ``--softcap C`` runs every batch size twice, without and with final-logit soft-capping (``final_logit_softcap=C``:
-elementwise ops on the step's [B, V] logits).  ``--model-only`` skips the kernel arms.
+elementwise ops on the step's [B, V] logits).  ``--sinks`` runs every batch size without and with attention sinks
+(``attn_sinks=True``: a second model of the same shape, its sinks drawn from N(0, 1)).  ``--model-only`` skips the
+kernel arms.
 Prints one JSON line per configuration.
 
 usage: python bench/decode_bench.py [--batches 1,16,64] [--prompt 128] [--new 256] [--kernels-only] [--softcap 30]
@@ -47,6 +49,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--softcap", type=float, default=None)
     ap.add_argument("--model-only", action="store_true")
+    ap.add_argument("--sinks", action="store_true")
     args = ap.parse_args()
     import torch
     from pretraining_llm_amd import ops
@@ -96,11 +99,19 @@ def main():
 
     torch.manual_seed(0)
     cfg = get_preset(args.model)
-    model = GPT(cfg).to(dev, torch.bfloat16).eval()
+    models = {False: GPT(cfg).to(dev, torch.bfloat16).eval()}
+    if args.sinks:
+        models[True] = GPT(cfg.replace(attn_sinks=True)).to(dev, torch.bfloat16).eval()
+        with torch.no_grad():
+            for blk in models[True].attn_blocks:
+                blk.attn.sinks.normal_()
     caps = [None] + ([args.softcap] if args.softcap else [])
-    for B, cap in ((int(b), c) for b in args.batches.split(",") for c in caps):
+    for B, cap, sk in ((int(b), c, s) for b in args.batches.split(",") for c in caps for s in models):
+        model, cfg = models[sk], models[sk].config.replace(final_logit_softcap=None)
         idx = torch.randint(0, cfg.vocab_size, (B, args.prompt), device=dev)
         res = {"model": args.model, "batch": B, "prompt": args.prompt, "new_tokens": args.new}
+        if args.sinks:
+            res["attn_sinks"] = sk
         if args.softcap:
             model.config = cfg.replace(final_logit_softcap=cap)  # no parameters: the same weights
             res["final_logit_softcap"] = cap

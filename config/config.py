@@ -100,6 +100,7 @@ default_config = {
     'sliding_window_pattern': None,   # 0: every layer local; n >= 2: every n-th layer global (None -> the preset's)
     'z_loss': None,                   # auxiliary z-loss coefficient: z_loss * logsumexp(logits)^2 per token, training only (None -> the preset's)
     'final_logit_softcap': None,      # cap: logits -> cap * tanh(logits / cap) before the softmax, training and generation (None -> the preset's)
+    'attn_sinks': None,               # True: one learned sink logit per query head in every softmax denominator (None -> the preset's)
     'override_preset_dims': False,    # with model_preset: the dims above (n_embed, n_head, n_blocks, ...) override the preset's
     'tuned_gemms': True,              # GPU: load the shipped TunableOp GEMM selections (pretraining_llm_amd/tuning/)
     'tp_size': 1,                     # tensor parallelism: heads / FFN columns sharded (parallel/model_parallel.py)

@@ -83,7 +83,9 @@ struct FwdCfg {
 // block skips tiles that end before its first row's bound, and tiles that begin before its last row's
 // bound take the per-element compare (against a second per-lane limit).  Rows whose first processed
 // tiles are wholly masked run with m = -inf through the guards of the lazy-max update below.
-template <int D, bool SEG>
+// SINK (a.sinks: one learned logit per query head that joins every row's softmax denominator and carries no
+// value, not multiplied by scale): only the epilogue differs -- the tile loop is the plain kernel's.
+template <int D, bool SEG, bool SINK>
 __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_kernel(AttnFwdArgs a) {
   using C = FwdCfg<D>;
   using I = Img<D>;
@@ -366,12 +368,27 @@ __global__ __launch_bounds__(64 * FwdCfg<D>::NW, FwdCfg<D>::MINB) void attn_fwd_
 #pragma unroll
   for (int j = 0; j < QB; ++j) {
     const int qi = qw[j] + r;
-    const float lt = l[j] + __shfl_xor(l[j], 32, 64);
+    float lt = l[j] + __shfl_xor(l[j], 32, 64);
+    float mt = m[j], osc = 1.f;
+    if constexpr (SINK) {
+      // m is lazy (up to kLazyThr below the row's true maximum), so the sink is folded against a fresh
+      // reference M = max(m, s2): lt' = lt 2^(m - M) + 2^(s2 - M), o scaled by 2^(m - M) / lt'.  The compares
+      // keep inf - inf out of the exponents: s2 = -inf leaves (m, lt, o) exactly as they are (bit-identical to
+      // the plain kernel), s2 = +inf gives o = 0, lse = +inf, and a row without keys (m = -inf) o = 0, lse = s.
+      const float s2 = bf2f(a.sinks[h]) * 1.4426950408889634f;  // h is workgroup-uniform: a scalar load
+      const float M = fmaxf(mt, s2);
+      if (M != -INFINITY) {
+        osc = mt == M ? 1.f : fast_exp2(mt - M);
+        lt = lt * osc + (s2 == M ? 1.f : fast_exp2(s2 - M));
+      }
+      mt = M;
+    }
     if (qi < a.T) {
-      const float inv = lt > 0.f ? 1.f / lt : 0.f;
+      float inv = lt > 0.f ? 1.f / lt : 0.f;
+      if constexpr (SINK) inv *= osc;
       store_row_bf16<NDB>(a.o + b * a.o_sb + (int64_t)qi * a.o_st + (int64_t)h * a.o_sh, o[j], inv, hh);
       if (hh == 0 && a.lse)
-        a.lse[((int64_t)b * a.H + h) * a.T + qi] = (m[j] + log2f(lt)) * 0.69314718055994531f;
+        a.lse[((int64_t)b * a.H + h) * a.T + qi] = (mt + log2f(lt)) * 0.69314718055994531f;
     }
   }
 }
@@ -1100,8 +1117,15 @@ template <int D>
 static void attn_fwd_t(const AttnFwdArgs& a, hipStream_t st) {
   const int nqb = (a.T + FwdCfg<D>::BM - 1) / FwdCfg<D>::BM;
   const dim3 grid(nqb * a.B * a.H), blk(64 * FwdCfg<D>::NW);
-  if (a.kv_start) hipLaunchKernelGGL((attn_fwd_kernel<D, true>), grid, blk, 0, st, a);
-  else hipLaunchKernelGGL((attn_fwd_kernel<D, false>), grid, blk, 0, st, a);
+  // (the sink is its own instantiation: the plain kernels keep their code and registers)
+  if (a.sinks) {
+    if (a.kv_start) hipLaunchKernelGGL((attn_fwd_kernel<D, true, true>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((attn_fwd_kernel<D, false, true>), grid, blk, 0, st, a);
+  } else if (a.kv_start) {
+    hipLaunchKernelGGL((attn_fwd_kernel<D, true, false>), grid, blk, 0, st, a);
+  } else {
+    hipLaunchKernelGGL((attn_fwd_kernel<D, false, false>), grid, blk, 0, st, a);
+  }
 }
 
 void attn_fwd(const AttnFwdArgs& a, hipStream_t st) {

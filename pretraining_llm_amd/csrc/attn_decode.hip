@@ -24,6 +24,10 @@
 //  * a sliding window (`window` > 0, a host constant of the layer) limits the keys to the last `window`
 //    rows [max(0, S - window), S) of the count: a local layer streams `window` cache rows per token, not
 //    the whole context, and the count stays on the device.
+//  * attention sinks (`sinks`, bf16 [H]: one logit per query head in the softmax denominator, no value, not
+//    scaled) enter once, at the last merge: in the workgroup's final merge when splits == 1, as one more partial
+//    of the combine kernel otherwise.  The key loop and the per-split partials are sink-free; a sequence without
+//    keys gives o = 0.
 #include "common.h"
 #include "kernels.h"
 
@@ -140,9 +144,14 @@ __global__ __launch_bounds__(NT) void attn_decode_kernel(DecodeArgs a) {
   __syncthreads();
   for (int i = t; i < G * D; i += NT) {
     const int g = i / D, d = i % D;
+    const int h = hk * G + g;
     float mx = -INFINITY;
 #pragma unroll
     for (int ww = 0; ww < 4; ++ww) mx = fmaxf(mx, s_ml[ww][g][0]);
+    // attention sink (one logit per query head in the denominator, no value): folded in here when this
+    // workgroup's merge is the last one; with splits > 1 the partials stay sink-free and the combine adds it
+    const float s2 = a.sinks && a.splits == 1 ? bf2f(a.sinks[h]) * 1.4426950408889634f : -INFINITY;
+    mx = fmaxf(mx, s2);
     float lsum = 0.f, o = 0.f;
 #pragma unroll
     for (int ww = 0; ww < 4; ++ww) {
@@ -150,7 +159,7 @@ __global__ __launch_bounds__(NT) void attn_decode_kernel(DecodeArgs a) {
       lsum += s_ml[ww][g][1] * c;
       o += s_acc[ww][g][d] * c;
     }
-    const int h = hk * G + g;
+    if (s2 != -INFINITY) lsum += s2 == mx ? 1.f : fast_exp2(s2 - mx);  // (no inf - inf at s2 = +inf)
     const float inv = lsum > 0.f ? 1.f / lsum : 0.f;
     if (a.splits == 1) {
       a.o[(int64_t)b * a.o_sb + (int64_t)h * a.o_sh + d] = f2bf_bits(o * inv);
@@ -170,8 +179,11 @@ __global__ __launch_bounds__(64) void attn_decode_combine_kernel(DecodeArgs a) {
   const float* lse = a.part_lse + (int64_t)bh * a.splits;
   float mx = -INFINITY;
   for (int s = 0; s < a.splits; ++s) mx = fmaxf(mx, lse[s]);
+  // the attention sink is one more partial: log2-sum-exp s2, output zero
+  const float s2 = a.sinks ? bf2f(a.sinks[h]) * 1.4426950408889634f : -INFINITY;
+  mx = fmaxf(mx, s2);
   float o[D / 64 > 0 ? D / 64 : 1] = {};
-  float wsum = 0.f;
+  float wsum = s2 == -INFINITY ? 0.f : (s2 == mx ? 1.f : fast_exp2(s2 - mx));
   for (int s = 0; s < a.splits; ++s) {
     const float c = mx == -INFINITY ? 0.f : fast_exp2(lse[s] - mx);
     wsum += c;

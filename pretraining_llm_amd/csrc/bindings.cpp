@@ -615,6 +615,38 @@ std::tuple<Tensor, Tensor> qk_norm_bwd_(Tensor& dqkv, const Tensor& qkv, const T
   return {dwq, dwk};
 }
 
+// Sink gradient ds[h] = -sum_{b,t} exp(s[h] - lse[b,h,t]) delta[b,h,t] (csrc/attn_sink.hip).  acc: the gradient is
+// added into (or, overwrite, stored to) this [H] slot and an empty tensor comes back; without it a fresh bf16 [H].
+Tensor attn_sink_bwd(const Tensor& lse, const Tensor& delta, const Tensor& sinks, const std::optional<Tensor>& acc,
+                     bool overwrite) {
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.dim() == 3 && lse.is_contiguous(),
+              "attn_sink_bwd: lse must be a contiguous fp32 [B, H, T] GPU tensor");
+  TORCH_CHECK(delta.device() == lse.device() && delta.scalar_type() == at::kFloat && delta.is_contiguous() &&
+                  delta.sizes() == lse.sizes(), "attn_sink_bwd: delta must be fp32 [B, H, T] like lse");
+  const int64_t B = lse.size(0), H = lse.size(1), T = lse.size(2);
+  TORCH_CHECK(sinks.device() == lse.device() && sinks.scalar_type() == at::kBFloat16 && sinks.dim() == 1 &&
+                  sinks.size(0) == H && sinks.is_contiguous(), "attn_sink_bwd: sinks must be bf16 [", H, "]");
+  check_aligned16(lse, "lse");
+  check_aligned16(delta, "delta");
+  TORCH_CHECK(B * T < (int64_t)1 << 31, "attn_sink_bwd: B * T must be below 2^31");
+  bool gf32 = false;
+  if (acc) {
+    gf32 = check_grad(*acc, "acc");
+    TORCH_CHECK(acc->numel() == H && acc->is_contiguous(), "attn_sink_bwd: accumulate target shape [", H, "]");
+  }
+  Tensor out = acc ? *acc : at::zeros({H}, sinks.options());
+  if (B * T > 0 && H > 0) {
+    const int G = pllm::attn_sink_bwd_grid((int)B, (int)T);
+    Tensor part = at::empty({G, H}, lse.options());
+    pllm::attn_sink_bwd(lse.data_ptr<float>(), delta.data_ptr<float>(), sinks.data_ptr(), (int)B, (int)H, (int)T,
+                        part.data_ptr<float>(), out.data_ptr(), gf32, acc.has_value() && !overwrite, cur_stream());
+  } else if (acc && overwrite) {
+    out.zero_();
+  }
+  if (acc) return at::empty({0}, sinks.options());
+  return out;
+}
+
 // x *= s in place (x bf16 or fp32, contiguous; s a 1-element fp32 GPU tensor); no pass at all when s == 1
 void scale_(Tensor& x, const Tensor& s) {
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat, "scale_: x bf16 or fp32");
@@ -1028,8 +1060,19 @@ static const int* check_bound(const std::optional<Tensor>& t, const Tensor& q, i
   return t->data_ptr<int>();
 }
 
+// Optional attention sinks of attn_fwd / attn_decode: bf16 [H] (one logit per query head), contiguous, on q's device
+static const uint16_t* check_sinks(const std::optional<Tensor>& t, const Tensor& q, int64_t H, const char* op) {
+  if (!t) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->device() == q.device(), op, ": sinks must be on the device of q");
+  TORCH_CHECK(t->scalar_type() == at::kBFloat16, op, ": sinks must be bf16");
+  TORCH_CHECK(t->dim() == 1 && t->size(0) == H, op, ": sinks must have shape [", H, "] (one per query head), got ",
+              t->sizes());
+  TORCH_CHECK(t->is_contiguous(), op, ": sinks must be contiguous");
+  return (const uint16_t*)t->data_ptr();
+}
+
 std::vector<Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, bool causal, double scale,
-                             const std::optional<Tensor>& kv_start) {
+                             const std::optional<Tensor>& kv_start, const std::optional<Tensor>& sinks) {
   const int64_t D = q.size(3);
   TORCH_CHECK(pllm::attn_supported_head_dim((int)D), "attention: head dim must be 32, 64 or 128, got ", D);
   check_head_view(q, "q", D);
@@ -1058,6 +1101,7 @@ std::vector<Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, 
   a.scale_log2 = (float)(scale * 1.4426950408889634);
   a.causal = causal ? 1 : 0;
   a.kv_start = check_bound(kv_start, q, B, T, S, T, causal, "kv_start");
+  a.sinks = check_sinks(sinks, q, H, "attn_fwd");
   // diagnostic (a PLLM_FWD_STAMPS=1 build of attention.hip + this env): per-wave phase cycles of
   // the forward's tile loop, summed and printed to stderr after the launch
   static const bool stamps = std::getenv("PLLM_FWD_STAMPS") != nullptr;
@@ -1084,8 +1128,9 @@ std::vector<Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, 
 // (any batch/row strides).  ``seqlen``: optional int32 device scalar overriding S (the
 // number of valid cache rows) so a captured decode step replays at every position.  ``window`` > 0
 // (sliding-window attention, a host constant): only the last ``window`` keys of the count are read.
+// ``sinks``: optional bf16 [H] attention sinks, in the denominator whatever the count or window (count 0: o = 0).
 Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, double scale, const c10::optional<Tensor>& seqlen,
-                   int64_t window) {
+                   int64_t window, const std::optional<Tensor>& sinks) {
   const int64_t D = q.size(3);
   check_head_view(q, "q", D);
   check_head_view(k, "k", D);
@@ -1097,7 +1142,7 @@ Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, double sca
   TORCH_CHECK(H % Hkv == 0 && pllm::attn_decode_supported((int)D, (int)(H / Hkv)),
               "attn_decode: head dim 32/64/128 and group size 1/2/4/8 supported");
   TORCH_CHECK(window >= 0, "attn_decode: window must be >= 0 (0 = no window)");
-  Tensor o = at::empty({B, 1, H, D}, q.options());
+  Tensor o = S > 0 ? at::empty({B, 1, H, D}, q.options()) : at::zeros({B, 1, H, D}, q.options());
   DecodeArgs a{};
   a.q = (const uint16_t*)q.data_ptr();
   a.k = (const uint16_t*)k.data_ptr();
@@ -1109,6 +1154,7 @@ Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, double sca
   a.v_sb = v.stride(0); a.v_st = v.stride(1); a.v_sh = v.stride(2);
   a.o_sb = o.stride(0); a.o_sh = o.stride(2);
   a.scale_log2 = (float)(scale * 1.4426950408889634);
+  a.sinks = check_sinks(sinks, q, H, "attn_decode");
   if (seqlen.has_value()) {
     TORCH_CHECK(seqlen->is_cuda() && seqlen->scalar_type() == at::kInt && seqlen->is_contiguous() &&
                     (seqlen->numel() == 1 || seqlen->numel() == B),
@@ -1147,7 +1193,8 @@ int64_t attn_bwd_ws_bytes() {
 void attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o, const Tensor& lse,
               Tensor& dq, Tensor& dk, Tensor& dv, bool causal, double scale, const std::optional<Tensor>& rope_cos,
               const std::optional<Tensor>& rope_sin, const std::optional<Tensor>& delta_in,
-              const std::optional<Tensor>& kv_start, const std::optional<Tensor>& q_last) {
+              const std::optional<Tensor>& kv_start, const std::optional<Tensor>& q_last,
+              const std::optional<Tensor>& delta_out) {
   const int64_t D = q.size(3);
   TORCH_CHECK(pllm::attn_supported_head_dim((int)D), "attention: head dim must be 32, 64 or 128");
   for (auto& pr : std::vector<std::pair<const Tensor*, const char*>>{
@@ -1163,7 +1210,12 @@ void attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor
   if (delta_in)
     TORCH_CHECK(delta_in->scalar_type() == at::kFloat && delta_in->is_contiguous() && delta_in->numel() == B * H * T,
                 "attn_bwd: delta [B, H, T] fp32");
-  Tensor delta = delta_in ? *delta_in : at::empty({B, H, T}, f32);
+  // delta_out: the caller keeps the delta that the pre-pass forms here (the sink gradient reads it again)
+  if (delta_out)
+    TORCH_CHECK(delta_out->is_cuda() && delta_out->device() == q.device() && delta_out->scalar_type() == at::kFloat &&
+                    delta_out->is_contiguous() && delta_out->numel() == B * H * T,
+                "attn_bwd: delta_out [B, H, T] fp32 on the device of q");
+  Tensor delta = delta_in ? *delta_in : (delta_out ? *delta_out : at::empty({B, H, T}, f32));
   // per-key-block bf16 dQ partial slabs (attention.hip: plain stores + ordered fp32 reduce, no
   // atomics), run in passes of at most `per` key blocks: the workspace is bounded by
   // PLLM_ATTN_BWD_WS_MB (default 4096 MiB: one pass for every shipped config -- passes split the
@@ -1301,9 +1353,10 @@ TORCH_LIBRARY(pllm, m) {
   m.def("transpose_run(Tensor desc, int total_tiles) -> ()");
   m.def("sample(Tensor logits, float temperature, int seed) -> Tensor");
   m.def("sample_rows(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor min_p, Tensor seed, Tensor step) -> (Tensor tokens, Tensor kept, Tensor min_kept)");
-  m.def("attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, Tensor? kv_start=None) -> Tensor[]");
-  m.def("attn_decode(Tensor q, Tensor k, Tensor v, float scale, Tensor? seqlen=None, int window=0) -> Tensor");
-  m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, Tensor? delta=None, Tensor? kv_start=None, Tensor? q_last=None) -> ()");
+  m.def("attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, Tensor? kv_start=None, Tensor? sinks=None) -> Tensor[]");
+  m.def("attn_decode(Tensor q, Tensor k, Tensor v, float scale, Tensor? seqlen=None, int window=0, Tensor? sinks=None) -> Tensor");
+  m.def("attn_sink_bwd(Tensor lse, Tensor delta, Tensor sinks, Tensor(a!)? acc, bool overwrite) -> Tensor");
+  m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, Tensor? delta=None, Tensor? kv_start=None, Tensor? q_last=None, Tensor(d!)? delta_out=None) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(pllm, CUDA, m) {
@@ -1339,6 +1392,7 @@ TORCH_LIBRARY_IMPL(pllm, CUDA, m) {
   m.impl("sample_rows", sample_rows);
   m.impl("attn_fwd", attn_fwd);
   m.impl("attn_decode", attn_decode);
+  m.impl("attn_sink_bwd", attn_sink_bwd);
   m.impl("gemv", gemv);
   m.impl("attn_bwd", attn_bwd);
 }

@@ -20,6 +20,9 @@ struct AttnFwdArgs {
   // optional per-row key bounds (document / window masks; causal, S == T): query i sees keys
   // kv_start[b, i] <= j <= i.  int32 [B, T], non-decreasing along T, 0 <= kv_start[i] <= i.  Null: plain causal
   const int* kv_start;
+  // optional attention sinks: bf16 [H], one logit per query head added to every row's softmax denominator
+  // (no value row, not scaled).  Null: plain softmax
+  const uint16_t* sinks;
 };
 
 // q [B, H, D] (one query per sequence), k/v rows of a [B, S_max, Hkv, D]-strided cache
@@ -33,6 +36,7 @@ struct DecodeArgs {
   int64_t q_sb, q_sh, k_sb, k_st, k_sh, v_sb, v_st, v_sh, o_sb, o_sh;
   float scale_log2;
   int window;                // sliding window: only the last `window` keys of the count are read (0 = all)
+  const uint16_t* sinks;     // optional attention sinks, bf16 [H] (see AttnFwdArgs), folded in once at the last merge
 };
 
 struct AttnBwdArgs {
@@ -232,5 +236,10 @@ int attn_decode_splits(int B, int Hkv, int S_max);
 void attn_decode(const DecodeArgs& a, hipStream_t st);
 void attn_fwd(const AttnFwdArgs& a, hipStream_t st);
 void attn_bwd(const AttnBwdArgs& a, hipStream_t st);
+// attn_sink.hip: sink gradient ds[h] = -sum_{b,t} exp(s[h] - lse[b,h,t]) delta[b,h,t] (lse, delta fp32 [B, H, T],
+// sinks bf16 [H]) through fp32 partials part [attn_sink_bwd_grid()][H] and col_reduce (deterministic)
+int attn_sink_bwd_grid(int B, int T);
+void attn_sink_bwd(const float* lse, const float* delta, const void* sinks, int B, int H, int T, float* part,
+                   void* out, bool out_f32, bool accumulate, hipStream_t st);
 
 }  // namespace pllm

@@ -63,6 +63,12 @@ class ModelConfig:
     # Both run inside the fused CE kernel; no parameters
     z_loss: float = 0.0
     final_logit_softcap: Optional[float] = None
+    # Attention sinks (StreamingLLM / gpt-oss): one learned logit per query head and block that joins every softmax
+    # row's denominator and carries no value, so a row may put probability on "nothing" ("softmax-off-by-one" when
+    # frozen at 0).  Not multiplied by the score scale; always visible, whatever window or document bounds the row
+    # has.  Architecture: training, recompute, KV-cache generation and the servers all apply it.  n_head parameters
+    # per block (1-D: no weight decay), initialised to 0.  Not with tensor / context parallelism
+    attn_sinks: bool = False
     init: str = "gpt2"                      # gpt2 | torch_default
     init_std: float = 0.02
     # True / False, a float fraction of the blocks, or "auto": checkpoint only as many blocks as
@@ -78,6 +84,9 @@ class ModelConfig:
         if self.qk_norm and self.arch == "ref":
             raise ValueError("qk_norm is not available with arch='ref': the reference checkpoint layout "
                              "(per-head key / query / value weights) has no place for the gains")
+        if self.attn_sinks and self.arch == "ref":
+            raise ValueError("attn_sinks is not available with arch='ref': the reference checkpoint layout "
+                             "(per-head key / query / value weights) has no place for the sink logits")
         if self.doc_mask and not 0 <= self.doc_sep_token < self.vocab_size:
             raise ValueError(f"doc_mask: doc_sep_token={self.doc_sep_token} is outside the vocabulary "
                              f"[0, {self.vocab_size})")
@@ -154,6 +163,8 @@ class ModelConfig:
         per += 2 * nparam_norm
         if self.qk_norm:
             per += 2 * self.head_dim
+        if self.attn_sinks:
+            per += self.n_head
         n = L * per + nparam_norm
         emb = V * C + (T * C if self.pos == "learned" else 0)
         if include_embedding:
@@ -237,6 +248,12 @@ PRESETS = {
     "llama-tiny-zloss": lambda: _llama(vocab_size=512, context_length=128, n_embed=128, n_head=4, n_blocks=2,
                                        n_kv_head=2, ffn_hidden=256, qk_norm=True, z_loss=1e-4,
                                        final_logit_softcap=30.0),
+    # the sliding-window pair with attention sinks (gpt-oss: local / global layers, one sink logit per head)
+    "llama-1.3b-sinks": lambda: _llama(vocab_size=50304, context_length=2048, n_embed=2048, n_head=16, n_blocks=24,
+                                       ffn_hidden=5504, sliding_window=512, sliding_window_pattern=4, attn_sinks=True),
+    "llama-tiny-sinks": lambda: _llama(vocab_size=512, context_length=128, n_embed=128, n_head=4, n_blocks=2,
+                                       n_kv_head=2, ffn_hidden=256, sliding_window=32, sliding_window_pattern=2,
+                                       attn_sinks=True),
 }
 
 

@@ -84,6 +84,13 @@ class Attention(nn.Module):
         self.qk_norm = bool(cfg.qk_norm)
         if self.qk_norm:  # only then: state dicts of models without QK-norm keep their keys
             self.q_norm, self.k_norm = HeadNorm(cfg.head_dim), HeadNorm(cfg.head_dim)
+        # attention sinks: one logit per query head in every softmax row's denominator, no value (ops.attention_packed)
+        self.attn_sinks = bool(cfg.attn_sinks)
+        if self.attn_sinks:  # only then, like the QK-norm gains; 1-D: exempt from weight decay (train/optim.py)
+            self.sinks = nn.Parameter(torch.zeros(cfg.n_head))
+
+    def _sinks_kw(self) -> dict:
+        return dict(sinks=self.sinks) if self.attn_sinks else {}
 
     def _qk_norm_kw(self) -> dict:
         if not self.qk_norm:
@@ -106,9 +113,10 @@ class Attention(nn.Module):
             r = residual if ops.resid_gemm_ok(residual, self.proj.weight) else None
             return ops.attention_proj(qkv, self.n_head, self.n_kv_head, self.proj.weight, self.proj.bias,
                                       rope_cos=cos, rope_sin=sin, bias_grad_external=fuse_out_bias,
-                                      residual=r, bounds=bounds, **self._qk_norm_kw()), r is not None
+                                      residual=r, bounds=bounds, **self._qk_norm_kw(),
+                                      **self._sinks_kw()), r is not None
         y = ops.attention_packed(qkv, self.n_head, self.n_kv_head, causal=True, rope_cos=cos, rope_sin=sin,
-                                 bounds=bounds, **self._qk_norm_kw())
+                                 bounds=bounds, **self._qk_norm_kw(), **self._sinks_kw())
         if self.proj is not None:
             r = residual if ops.resid_gemm_ok(residual, self.proj.weight) else None
             return ops.linear(y, self.proj.weight, self.proj.bias, bias_grad_external=fuse_out_bias,
@@ -138,11 +146,13 @@ class Attention(nn.Module):
             raise NotImplementedError(f"sliding_window: a cached step of T={T} > 1 tokens at pos={pos} > 0 (chunked "
                                       "prefill) is not supported in a local layer")
         if W is not None and T > 1 and W < T:  # prefill from position 0 (S == T): per-row key bounds
-            y = ops.attention(q.contiguous(), kc, vc, causal=True, kv_start=ops.window_bounds(B, T, W, q.device)[0])
+            y = ops.attention(q.contiguous(), kc, vc, causal=True, kv_start=ops.window_bounds(B, T, W, q.device)[0],
+                              **self._sinks_kw())
         elif W is not None and T == 1:  # one token: the last W rows of the cache view
-            y = ops.attention(q.contiguous(), kc[:, max(0, pos + 1 - W):], vc[:, max(0, pos + 1 - W):], causal=True)
+            y = ops.attention(q.contiguous(), kc[:, max(0, pos + 1 - W):], vc[:, max(0, pos + 1 - W):], causal=True,
+                              **self._sinks_kw())
         else:
-            y = ops.attention(q.contiguous(), kc, vc, causal=True)
+            y = ops.attention(q.contiguous(), kc, vc, causal=True, **self._sinks_kw())
         y = y.reshape(B, T, H * D)
         if self.proj is not None:
             y = ops.linear(y, self.proj.weight, self.proj.bias)
@@ -187,7 +197,7 @@ class Attention(nn.Module):
                 cache.k[layer_idx].index_copy_(1, pos_t, k)
                 cache.v[layer_idx].index_copy_(1, pos_t, v)
         y = ops.attention_decode(q.contiguous(), cache.k[layer_idx], cache.v[layer_idx], seqlen=len_t,
-                                 window=self.window)
+                                 window=self.window, **self._sinks_kw())
         y = y.reshape(B, 1, H * D)
         if self.proj is not None:
             y = ops.linear(y, self.proj.weight, self.proj.bias)
@@ -367,7 +377,7 @@ class GPT(nn.Module):
         proj_std = std / math.sqrt(2 * cfg.n_blocks)
         for name, p in self.named_parameters():
             if p.dim() == 1:
-                if name.endswith("bias"):
+                if name.endswith("bias") or name.endswith("attn.sinks"):
                     nn.init.zeros_(p)
                 else:
                     nn.init.ones_(p)

@@ -730,11 +730,12 @@ def _bounds_mask(kv_start):
     return ((j[None, None, :] >= kv_start[:, :, None]) & (j[None, None, :] <= j[None, :, None])).unsqueeze(1)
 
 
-def _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, qkn=None, kv_start=None):
+def _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, qkn=None, kv_start=None, sinks=None):
     """Forward attention over packed qkv -> (qk, o, lse, rstd); ``qk`` is the q / k buffer of the
     pre-pass ([B, T, (H + Hkv) D], None without one), which the backward reads again: rotated (RoPE,
     rope_qk) or, with ``qkn`` = (wq, wk, eps) (QK-norm), normalised per head and then rotated when
-    there are tables (qk_norm_rope, which also returns the heads' ``rstd``; else None)."""
+    there are tables (qk_norm_rope, which also returns the heads' ``rstd``; else None).  ``sinks``: bf16 [H]
+    attention sinks, folded into the forward kernel's epilogue (``lse`` then includes them)."""
     T = qkv.shape[1]
     D = qkv.shape[2] // (H + 2 * Hkv)
     rstd = None
@@ -743,7 +744,7 @@ def _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, qkn=None, kv_start=No
     else:
         qk = _ops().rope_qk(qkv, cos, sin, H + 2 * Hkv, H + Hkv, T) if cos is not None else None
     q, k, v = _qkv_heads(qkv, qk, H, Hkv, D)
-    o, lse = _ops().attn_fwd(q, k, v, causal, scale, kv_start)
+    o, lse = _ops().attn_fwd(q, k, v, causal, scale, kv_start, sinks)
     return qk, o, lse, rstd
 
 
@@ -764,21 +765,47 @@ def _qk_norm_bwd(dqkv, qkv, rstd, wq, wk, H, Hkv):
     return None, None
 
 
-def _attn_packed_bwd(do, qkv, qk, o, lse, cfg, cos, sin, delta=None, qkn=None, rstd=None, kv_start=None, q_last=None):
+def _sinks_kw(sinks) -> dict:
+    """The reference's ``sinks`` argument, only when there are sinks (without them the call is the plain one)."""
+    return {} if sinks is None else {"sinks": sinks}
+
+
+def _sink_bwd(lse, delta, sinks):
+    """Gradient of the attention sinks, ds[h] = -sum_{b,i} exp(s[h] - lse[b,h,i]) delta[b,h,i] (csrc/attn_sink.hip):
+    None when it went straight into the flat-gradient slot (the whole gradient at once: ``_set_target``), else
+    a fresh tensor."""
+    tgt, fresh = _set_target(sinks)
+    if tgt is None:
+        return _ops().attn_sink_bwd(lse, delta, sinks, None, False)
+    _ops().attn_sink_bwd(lse, delta, sinks, tgt, fresh)
+    _notify(sinks)
+    return None
+
+
+def _attn_packed_bwd(do, qkv, qk, o, lse, cfg, cos, sin, delta=None, qkn=None, rstd=None, kv_start=None, q_last=None,
+                     sinks=None):
     """Backward attention -> packed dqkv (for the unrotated qkv: the kernels rotate dq / dk back).
     ``do``: [B, T, H, D] contiguous; ``delta``: rowsum(dO * O) when the caller already holds it.
-    Returns (dqkv, dwq, dwk): with ``qkn`` = (wq, wk, eps) one streaming post-pass takes the q / k
-    columns back through the QK-norm and yields the gain gradients (see _qk_norm_bwd), else None."""
+    Returns (dqkv, dwq, dwk, dsinks): with ``qkn`` = (wq, wk, eps) one streaming post-pass takes the q / k
+    columns back through the QK-norm and yields the gain gradients (see _qk_norm_bwd), else None.  With ``sinks``
+    (``lse`` includes them) the backward kernels run as they are -- the sink has a zero value row, so
+    delta = rowsum(dO O) already is the sum of P dP over keys and sink -- and the sink gradient is one
+    reduction over lse and delta (see _sink_bwd), delta kept from the kernels' pre-pass when none came in."""
     H, Hkv, D, causal, scale = cfg
     q, k, v = _qkv_heads(qkv, qk, H, Hkv, D)
     dqkv = torch.empty_like(qkv)
     dq, dk, dv = _split_qkv(dqkv, H, Hkv, D)
     _attn_ws(qkv.device)
-    _ops().attn_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, cos, sin, delta, kv_start, q_last)
+    if sinks is not None and delta is None:
+        delta = torch.empty_like(lse)
+        _ops().attn_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, cos, sin, None, kv_start, q_last, delta)
+    else:
+        _ops().attn_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, cos, sin, delta, kv_start, q_last)
     dwq = dwk = None
     if qkn is not None:
         dwq, dwk = _qk_norm_bwd(dqkv, qkv, rstd, qkn[0], qkn[1], H, Hkv)
-    return dqkv, dwq, dwk
+    dsinks = _sink_bwd(lse, delta, sinks) if sinks is not None else None
+    return dqkv, dwq, dwk, dsinks
 
 
 class _FlashAttnPacked(torch.autograd.Function):
@@ -790,10 +817,12 @@ class _FlashAttnPacked(torch.autograd.Function):
     backward at the llama shape -- the round-2 RoPE A/B record under profiles/ -- and was removed.)"""
 
     @staticmethod
-    def forward(ctx, qkv, H, Hkv, causal, scale, cos, sin, wq=None, wk=None, qk_eps=1e-5, kv_start=None, q_last=None):
+    def forward(ctx, qkv, H, Hkv, causal, scale, cos, sin, wq=None, wk=None, qk_eps=1e-5, kv_start=None, q_last=None,
+                sinks=None):
         B, T, W = qkv.shape
         ctx.qkn = (wq, wk, qk_eps) if wq is not None else None  # QK-norm gains (the parameters themselves)
-        qk, o, lse, rstd = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, ctx.qkn, kv_start)
+        ctx.sinks = sinks  # attention sinks (the parameter itself)
+        qk, o, lse, rstd = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, ctx.qkn, kv_start, sinks)
         ctx.save_for_backward(qkv, qk, o, lse, cos, sin, rstd, kv_start, q_last)
         ctx.cfg = (H, Hkv, W // (H + 2 * Hkv), causal, scale)
         return o.view(B, T, -1)
@@ -801,10 +830,11 @@ class _FlashAttnPacked(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         qkv, qk, o, lse, cos, sin, rstd, kv_start, q_last = ctx.saved_tensors
-        dqkv, dwq, dwk = _attn_packed_bwd(do.contiguous().view(o.shape), qkv, qk, o, lse, ctx.cfg, cos, sin,
-                                          qkn=ctx.qkn, rstd=rstd, kv_start=kv_start, q_last=q_last)
-        ctx.qkn = None
-        return dqkv, None, None, None, None, None, None, dwq, dwk, None, None, None
+        dqkv, dwq, dwk, dsinks = _attn_packed_bwd(do.contiguous().view(o.shape), qkv, qk, o, lse, ctx.cfg, cos, sin,
+                                                  qkn=ctx.qkn, rstd=rstd, kv_start=kv_start, q_last=q_last,
+                                                  sinks=ctx.sinks)
+        ctx.qkn = ctx.sinks = None
+        return dqkv, None, None, None, None, None, None, dwq, dwk, None, None, None, dsinks
 
 
 class _AttnProjFn(torch.autograd.Function):
@@ -816,11 +846,12 @@ class _AttnProjFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, H, Hkv, causal, scale, cos, sin, w, b, bias_ext, res=None, wq=None, wk=None, qk_eps=1e-5,
-                kv_start=None, q_last=None):
+                kv_start=None, q_last=None, sinks=None):
         B, T, W = qkv.shape
         D = W // (H + 2 * Hkv)
         ctx.qkn = (wq, wk, qk_eps) if wq is not None else None  # QK-norm gains (the parameters themselves)
-        qk, o, lse, rstd = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, ctx.qkn, kv_start)
+        ctx.sinks = sinks  # attention sinks (the parameter itself)
+        qk, o, lse, rstd = _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, ctx.qkn, kv_start, sinks)
         ctx.save_for_backward(qkv, qk, o, lse, cos, sin, rstd, kv_start, q_last)
         ctx.cfg = (H, Hkv, D, causal, scale)
         ctx.w, ctx.b, ctx.bias_ext = w, b, bias_ext
@@ -834,8 +865,8 @@ class _AttnProjFn(torch.autograd.Function):
     def backward(ctx, dy):
         qkv, qk, o, lse, cos, sin, rstd, kv_start, q_last = ctx.saved_tensors
         H, Hkv, D, causal, scale = ctx.cfg
-        w, b, qkn = ctx.w, ctx.b, ctx.qkn
-        ctx.w = ctx.b = ctx.qkn = None
+        w, b, qkn, sinks = ctx.w, ctx.b, ctx.qkn, ctx.sinks
+        ctx.w = ctx.b = ctx.qkn = ctx.sinks = None
         B, T, _ = qkv.shape
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
         o2 = o.view(B * T, H * D)
@@ -844,10 +875,10 @@ class _AttnProjFn(torch.autograd.Function):
                                      ctx.needs_input_grad[8] and not ctx.bias_ext)
         # dO and delta from one GEMM through W_o's transposed shadow
         do2, delta = _ops().gemm_tn(dy2, _shadow_or_t(w), None, 6, o2, None, T)
-        dqkv, dwq, dwk = _attn_packed_bwd(do2.view(B, T, H, D), qkv, qk, o, lse, ctx.cfg, cos, sin, delta,
-                                          qkn=qkn, rstd=rstd, kv_start=kv_start, q_last=q_last)
+        dqkv, dwq, dwk, dsinks = _attn_packed_bwd(do2.view(B, T, H, D), qkv, qk, o, lse, ctx.cfg, cos, sin, delta,
+                                                  qkn=qkn, rstd=rstd, kv_start=kv_start, q_last=q_last, sinks=sinks)
         return (dqkv, None, None, None, None, None, None, dw, db, None, (dy if ctx.has_res else None), dwq, dwk,
-                None, None, None)
+                None, None, None, dsinks)
 
 
 # PLLM_AB attn_proj_fused=0: the output projection's backward on hipBLASLt + the attention's delta pre-pass
@@ -871,9 +902,9 @@ def attn_proj_ok(qkv, n_head: int, n_kv_head: int, w, b) -> bool:
 
 def attention_proj(qkv, n_head: int, n_kv_head: int, w, b, causal: bool = True, scale: Optional[float] = None,
                    rope_cos=None, rope_sin=None, bias_grad_external: bool = False, residual=None,
-                   q_norm_weight=None, k_norm_weight=None, qk_norm_eps: float = 1e-5, bounds=None):
+                   q_norm_weight=None, k_norm_weight=None, qk_norm_eps: float = 1e-5, bounds=None, sinks=None):
     """``linear(attention_packed(qkv, ...), w, b)`` (+ ``residual``, added by the GEMM) with the fused
-    backward (see _AttnProjFn).  ``bounds``: see attention_packed."""
+    backward (see _AttnProjFn).  ``bounds``, ``sinks``: see attention_packed."""
     D = qkv.shape[-1] // (n_head + 2 * n_kv_head)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     kv_start, q_last = bounds if bounds is not None else (None, None)
@@ -883,7 +914,7 @@ def attention_proj(qkv, n_head: int, n_kv_head: int, w, b, causal: bool = True, 
         qkv = qkv.contiguous()
     return _AttnProjFn.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin, w, b,
                              _bias_ext(bias_grad_external, b), residual, q_norm_weight, k_norm_weight, qk_norm_eps,
-                             kv_start, q_last)
+                             kv_start, q_last, sinks)
 
 
 _ATTN_WS_MB = [None]
@@ -981,12 +1012,14 @@ def qk_norm_packed(qkv, wq, wk, eps: float, n_head: int, n_kv_head: int, cos=Non
 
 def attention_packed(qkv, n_head: int, n_kv_head: int, causal: bool = True, scale: Optional[float] = None,
                      rope_cos: Optional[torch.Tensor] = None, rope_sin: Optional[torch.Tensor] = None,
-                     q_norm_weight=None, k_norm_weight=None, qk_norm_eps: float = 1e-5, bounds=None):
+                     q_norm_weight=None, k_norm_weight=None, qk_norm_eps: float = 1e-5, bounds=None, sinks=None):
     """Causal self-attention over a packed qkv tensor. RoPE (if cos/sin given) is
     applied to the q and k heads first (rotate-half convention); with ``q_norm_weight`` /
     ``k_norm_weight`` (QK-norm) every q and k head is RMS-normalised over D before that.
     ``bounds`` = (kv_start, q_last) (int32 [B, T] each, from ``doc_bounds`` / ``bounds_from_start``; needs
-    ``causal``): position i attends to keys kv_start[b, i] <= j <= i only (document / window masks)."""
+    ``causal``): position i attends to keys kv_start[b, i] <= j <= i only (document / window masks).
+    ``sinks`` [n_head] (attention sinks): one learned logit per query head that joins every row's softmax
+    denominator -- unscaled, visible whatever the bounds -- and carries no value; differentiable."""
     B, T, W = qkv.shape
     D = W // (n_head + 2 * n_kv_head)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
@@ -1000,7 +1033,7 @@ def attention_packed(qkv, n_head: int, n_kv_head: int, causal: bool = True, scal
         else:  # QK-norm: qk_norm_rope is that pre-pass, qk_norm_bwd_ a post-pass over dqkv, both on contiguous qkv
             qkv = qkv.contiguous()
         return _FlashAttnPacked.apply(qkv, n_head, n_kv_head, causal, scale, rope_cos, rope_sin,
-                                      q_norm_weight, k_norm_weight, qk_norm_eps, kv_start, q_last)
+                                      q_norm_weight, k_norm_weight, qk_norm_eps, kv_start, q_last, sinks)
     if q_norm_weight is not None:
         q, k = qk_norm_packed(qkv, q_norm_weight, k_norm_weight, qk_norm_eps, n_head, n_kv_head, rope_cos, rope_sin)
         v = _split_qkv(qkv, n_head, n_kv_head, D)[2]
@@ -1008,7 +1041,7 @@ def attention_packed(qkv, n_head: int, n_kv_head: int, causal: bool = True, scal
         if rope_cos is not None:
             qkv = rope_packed(qkv, rope_cos, rope_sin, n_head, n_kv_head)
         q, k, v = _split_qkv(qkv, n_head, n_kv_head, D)
-    if _stock("attn") and qkv.is_cuda:
+    if _stock("attn") and qkv.is_cuda and sinks is None:  # (SDPA has no sink: those go through the reference)
         # stock-PyTorch baseline path (SDPA), used only by the explicit torch backend
         qh, kh, vh = (t.transpose(1, 2) for t in (q, k, v))
         if bounds is not None:  # the bounds as a boolean mask (it includes the causal triangle)
@@ -1018,16 +1051,17 @@ def attention_packed(qkv, n_head: int, n_kv_head: int, causal: bool = True, scal
             o = F.scaled_dot_product_attention(qh, kh, vh, is_causal=causal, scale=scale,
                                                enable_gqa=(n_kv_head != n_head))
         return o.transpose(1, 2).reshape(B, T, n_head * D)
-    o, _ = ref.attention(q, k, v, causal=causal, scale=scale, bounds=bounds)
+    o, _ = ref.attention(q, k, v, causal=causal, scale=scale, bounds=bounds, **_sinks_kw(sinks))
     return o.reshape(B, T, n_head * D)
 
 
 def attention(q, k, v, causal: bool = True, scale: Optional[float] = None, return_lse: bool = False,
-              kv_start: Optional[torch.Tensor] = None):
+              kv_start: Optional[torch.Tensor] = None, sinks: Optional[torch.Tensor] = None):
     """Unpacked attention q [B,T,H,D], k/v [B,S,Hkv,D] (forward only; used by the
     KV-cache decode and context-parallel paths).  Queries are aligned to the end
     of the key sequence.  ``kv_start`` (int32 [B, T], see ``window_bounds``; needs ``causal`` and S == T, a
-    prefill from position 0): query i sees keys kv_start[b, i] <= j <= i only."""
+    prefill from position 0): query i sees keys kv_start[b, i] <= j <= i only.  ``sinks`` [H]: attention sinks
+    (see ``attention_packed``); the returned lse includes them."""
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     if kv_start is not None:
@@ -1035,40 +1069,41 @@ def attention(q, k, v, causal: bool = True, scale: Optional[float] = None, retur
             raise ValueError(f"attention: kv_start needs causal attention over as many keys as queries "
                              f"(causal={causal}, T={q.shape[1]}, S={k.shape[1]})")
         if _hip(q):
-            o, lse = _ops().attn_fwd(q, k, v, causal, scale, kv_start)
+            o, lse = _ops().attn_fwd(q, k, v, causal, scale, kv_start, sinks)
         else:
-            o, lse = ref.attention(q, k, v, causal=True, scale=scale, bounds=(kv_start, None))
+            o, lse = ref.attention(q, k, v, causal=True, scale=scale, bounds=(kv_start, None), **_sinks_kw(sinks))
         return (o, lse) if return_lse else o
     if _hip(q) and q.shape[1] == 1 and not return_lse and q.shape[2] // k.shape[2] in (1, 2, 4, 8):
         # one query per sequence (KV-cache decode): split-KV streaming kernel (csrc/attn_decode.hip)
-        return _ops().attn_decode(q, k, v, scale)
+        return _ops().attn_decode(q, k, v, scale, None, 0, sinks)
     if _hip(q):
-        o, lse = _ops().attn_fwd(q, k, v, causal, scale)
+        o, lse = _ops().attn_fwd(q, k, v, causal, scale, None, sinks)
     else:
-        o, lse = ref.attention(q, k, v, causal=causal, scale=scale)
+        o, lse = ref.attention(q, k, v, causal=causal, scale=scale, **_sinks_kw(sinks))
     return (o, lse) if return_lse else o
 
 
 def attention_decode(q, k, v, seqlen: Optional[torch.Tensor] = None, scale: Optional[float] = None,
-                     window: Optional[int] = None):
+                     window: Optional[int] = None, sinks: Optional[torch.Tensor] = None):
     """Single-query attention q [B,1,H,D] over cached k/v [B,S,Hkv,D]; ``seqlen`` (int32 [1]
     device tensor) optionally limits the keys to the first ``seqlen`` rows, read on the
     device so a captured decode step (hipGraph) replays at every position.  ``window`` (sliding-window
-    attention, a host constant): only the last ``window`` of those keys, [max(0, n - window), n), are seen."""
+    attention, a host constant): only the last ``window`` of those keys, [max(0, n - window), n), are seen.
+    ``sinks`` [H]: attention sinks (see ``attention_packed``), in the denominator whatever the count or window."""
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     if window is not None and window < 1:
         raise ValueError(f"attention_decode: window={window} must be >= 1 (None: no window)")
     if _hip(q):
-        return _ops().attn_decode(q, k, v, scale, seqlen, int(window or 0))
+        return _ops().attn_decode(q, k, v, scale, seqlen, int(window or 0), sinks)
     W = window if window is not None else k.shape[1]
     if seqlen is not None and seqlen.numel() > 1:  # one key count per sequence
         return torch.cat([ref.attention(q[b:b + 1], k[b:b + 1, max(0, int(n) - W):int(n)],
                                         v[b:b + 1, max(0, int(n) - W):int(n)], causal=False,
-                                        scale=scale)[0] for b, n in enumerate(seqlen.tolist())])
+                                        scale=scale, **_sinks_kw(sinks))[0] for b, n in enumerate(seqlen.tolist())])
     n = int(seqlen.item()) if seqlen is not None else k.shape[1]
     k, v = k[:, max(0, n - W):n], v[:, max(0, n - W):n]
-    o, _ = ref.attention(q, k, v, causal=False, scale=scale)
+    o, _ = ref.attention(q, k, v, causal=False, scale=scale, **_sinks_kw(sinks))
     return o
 
 

@@ -178,17 +178,21 @@ def register() -> None:
                 logits.new_empty((B,), dtype=torch.float32))
 
     @_reg("attn_fwd")
-    def _(q, k, v, causal, scale, kv_start=None):
+    def _(q, k, v, causal, scale, kv_start=None, sinks=None):
         B, T, H, _ = q.shape
         return [q.new_empty(q.shape), q.new_empty((B, H, T), dtype=f32)]
 
     @_reg("attn_decode")
-    def _(q, k, v, scale, seqlen=None, window=0):
+    def _(q, k, v, scale, seqlen=None, window=0, sinks=None):
         return q.new_empty(q.shape)
+
+    @_reg("attn_sink_bwd")
+    def _(lse, delta, sinks, acc, overwrite):
+        return sinks.new_empty((0,) if acc is not None else (sinks.numel(),))
 
     @_reg("attn_bwd")
     def _(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, rope_cos=None, rope_sin=None, delta=None,
-          kv_start=None, q_last=None):
+          kv_start=None, q_last=None, delta_out=None):
         return None
 
     @_reg("gemv")

@@ -54,9 +54,17 @@ def _bounds_visible(bounds, causal: bool, T: int, S: int):
     return (j[None, None, :] >= kv_start[:, :, None]).unsqueeze(1)
 
 
-def attention(q, k, v, causal: bool = True, scale: Optional[float] = None, bounds=None):
+def _with_sink(s, sinks):
+    """Scores [B,H,T,S] with the heads' sink logits [H] appended as one more (always visible, unscaled) column."""
+    B, H, T, _ = s.shape
+    return torch.cat([s, sinks.to(s.dtype).view(1, H, 1, 1).expand(B, H, T, 1)], dim=-1)
+
+
+def attention(q, k, v, causal: bool = True, scale: Optional[float] = None, bounds=None, sinks=None):
     """q: [B,T,H,D], k/v: [B,S,Hkv,D] -> out [B,T,H,D], lse [B,H,T] (natural log).
-    ``bounds`` = (kv_start, q_last), int [B, T] each: query i sees keys kv_start[b, i] <= j <= i only."""
+    ``bounds`` = (kv_start, q_last), int [B, T] each: query i sees keys kv_start[b, i] <= j <= i only.
+    ``sinks`` [H]: attention sinks, one logit per query head that joins every row's softmax denominator (not
+    multiplied by ``scale``, visible whatever the masks) and carries no value; ``lse`` includes it."""
     B, T, H, D = q.shape
     S, Hkv = k.shape[1], k.shape[2]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
@@ -75,17 +83,19 @@ def attention(q, k, v, causal: bool = True, scale: Optional[float] = None, bound
         s = s.masked_fill(~mask, float("-inf"))
     if bounds is not None:
         s = s.masked_fill(~_bounds_visible(bounds, causal, T, S), float("-inf"))
-    lse = torch.logsumexp(s, dim=-1)                    # B,H,T
+    lse = torch.logsumexp(s if sinks is None else _with_sink(s, sinks), dim=-1)  # B,H,T
     p = torch.exp(s - lse.unsqueeze(-1))
     o = torch.matmul(p, vf)                             # B,H,T,D
     return o.transpose(1, 2).to(q.dtype), lse
 
 
-def attention_bwd(do, q, k, v, o, lse, causal: bool = True, scale: Optional[float] = None, bounds=None):
+def attention_bwd(do, q, k, v, o, lse, causal: bool = True, scale: Optional[float] = None, bounds=None, sinks=None):
     """Flash-style backward of one attention block given the row statistics of the WHOLE
     softmax (``lse`` [B,H,T], natural log, and the final output ``o``), so partial key
     blocks (ring / context parallel) produce exact partial gradients.
-    Returns fp32 (dq [B,T,H,D], dk [B,S,Hkv,D], dv [B,S,Hkv,D])."""
+    Returns fp32 (dq [B,T,H,D], dk [B,S,Hkv,D], dv [B,S,Hkv,D]).  With ``sinks`` [H] (``lse`` then includes the
+    sink) also dsinks [H]: the sink's value row is zero, so dS_sink = -p_sink delta and
+    dsinks[h] = -sum_{b,i} exp(sinks[h] - lse[b,h,i]) delta[b,h,i]; dq / dk / dv need nothing else."""
     B, T, H, D = q.shape
     S, Hkv = k.shape[1], k.shape[2]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
@@ -108,6 +118,9 @@ def attention_bwd(do, q, k, v, o, lse, causal: bool = True, scale: Optional[floa
     dk = torch.matmul(ds.transpose(-1, -2), qf) * scale
     dk = dk.view(B, Hkv, rep, S, D).sum(2)
     dv = dv.view(B, Hkv, rep, S, D).sum(2)
+    if sinks is not None:
+        dsinks = -(torch.exp(sinks.float().view(1, H, 1) - lse.float()) * delta.squeeze(-1)).sum((0, 2))
+        return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), dsinks
     return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2)
 
 

@@ -315,6 +315,10 @@ def parallelize_gpt(model, pg: ParallelGroups):
         # TP: the replicated gains see only the local heads, so their gradients would need a TP-group sum
         # (sync_replicated_grads covers sequence parallelism only); CP: ring / Ulysses attention take their own path
         raise ValueError(f"qk_norm is not supported with tensor or context parallelism (tp={pg.tp}, cp={pg.cp})")
+    if cfg.attn_sinks and (pg.tp > 1 or pg.cp > 1):
+        # CP: the ring merge combines LSEs of partial rows and would count the sink once per shard; TP: the sink
+        # logits would need sharding with the heads
+        raise ValueError(f"attn_sinks is not supported with tensor or context parallelism (tp={pg.tp}, cp={pg.cp})")
     for blk in model.attn_blocks:
         if pg.tp > 1:
             blk.attn = TPAttention(blk.attn, cfg, pg)

@@ -45,7 +45,7 @@ def model_config_from(cfg: dict) -> ModelConfig:
     dims = {k: cfg[k] for k in ("vocab_size", "context_length", "n_embed", "n_head", "n_blocks") if k in cfg}
     extra = {k: cfg[k] for k in ("n_kv_head", "ffn_hidden", "activation_checkpointing", "qk_norm", "qk_norm_eps",
                                   "doc_mask", "doc_sep_token", "sliding_window", "sliding_window_pattern", "z_loss",
-                                  "final_logit_softcap")
+                                  "final_logit_softcap", "attn_sinks")
              if cfg.get(k) is not None}
     if preset:
         mc = get_preset(preset)
@@ -70,6 +70,10 @@ def check_parallel_config(cfg: dict) -> None:
         raise ValueError(f"qk_norm is not supported with tensor or context parallelism (tp_size={tp}, "
                          f"cp_size={cp}): under TP the replicated gains see only the local heads and their "
                          "gradients would need a TP-group sum; ring / Ulysses attention take their own path")
+    if (tp > 1 or cp > 1) and model_config_from(cfg).attn_sinks:
+        raise ValueError(f"attn_sinks is not supported with tensor or context parallelism (tp_size={tp}, "
+                         f"cp_size={cp}): the ring merge combines LSEs of partial rows and would count the sink "
+                         "once per shard; under TP the sink logits would need sharding with the heads")
 
 
 def lr_at(step: int, cfg: dict) -> float:
