@@ -24,6 +24,21 @@ choice on the same box without a rebuild.  The C++ side reads the same variable 
 | ce_nt | 1 | 0: plain (not non-temporal) dlogits stores in the CE kernel | csrc/cross_entropy.hip (2,493 vs 2,524 us) |
 | tune_ms / tune_iters | 4 / 8 | TunableOp search budget (scripts/tune_gemms.py) | utils/gemm_tuning.py |
 | lt_verbose | 0 | 1: print hipBLASLt's candidate timings | -- |
+
+When a key is read -- setting PLLM_AB later than that does nothing for it:
+
+* at import of ``pretraining_llm_amd.ops``, frozen into a module constant: resid_gemm (``RESID_GEMM``), attn_proj_fused
+  (``FUSED_ATTN_PROJ``), fused_swiglu_fwd (``FUSED_SWIGLU_FWD``), lt_relu (``LT_RELU_FWD``), wgrad_bias
+  (``FUSED_WGRAD_BIAS``), ce_chunk_rows (``CE_CHUNK_ROWS``).  The ops read the constant on every call, so a test
+  flips one with ``monkeypatch.setattr(ops, "FUSED_WGRAD_BIAS", False)``, not through the environment;
+* once per process: wgrad_variant, wgrad_hy and gemm_persistent when the extension is loaded (ops/_lib.py); ce_nt at
+  the first cross-entropy launch (a C++ static);
+* when the object that uses it is built: wt_shadow and lazy_zero (FlatAdamW), dp_world1 (DataParallel),
+  gemm_persistent again (the captured train step), tune_ms / tune_iters (when tuning is switched on);
+* on every call: wgrad_hy_cost and lt_verbose (C++).
+
+The C++ parser matches ``key=`` exactly (blanks only before the key), this one also strips blanks around the key and
+the value: write ``key=value`` without blanks so that both sides read the same.
 """
 from __future__ import annotations
 
@@ -41,7 +56,8 @@ def _parse() -> dict:
 
 def ab(key: str, default):
     """The PLLM_AB value of ``key`` converted to ``default``'s type (bool: "1"/"0"), else ``default``.
-    Read on every call, so a test can monkeypatch the variable before constructing the object that reads it."""
+    The variable is parsed on every call of ``ab``; most callers call it once and keep the result (the module
+    docstring lists which), so a test monkeypatches those results, or the variable before the object is built."""
     v = _parse().get(key)
     if v is None:
         return default

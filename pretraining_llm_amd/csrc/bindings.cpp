@@ -32,12 +32,14 @@ void check_aligned16(const Tensor& t, const char* name) {
   TORCH_CHECK((reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0, name, " must be 16-byte aligned");
 }
 const void* opt_ptr(const std::optional<Tensor>& t) { return t.has_value() ? t->data_ptr() : nullptr; }
-// gradient accumulation targets (views of the optimizer's flat gradient): bf16 or fp32;
-// returns true for fp32
-bool check_grad(const Tensor& t, const char* name) {
+// gradient accumulation targets (views of the optimizer's flat gradient): bf16 or fp32, `numel` contiguous
+// elements; returns true for fp32
+bool check_grad(const Tensor& t, int64_t numel, const char* name) {
   check_gpu(t, name);
   TORCH_CHECK(t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kFloat, name,
               " must be bfloat16 or float32, got ", t.scalar_type());
+  TORCH_CHECK(t.numel() == numel && t.is_contiguous(), name, " shape: accumulate target of ", numel,
+              " contiguous elements, got ", t.sizes());
   return t.scalar_type() == at::kFloat;
 }
 
@@ -94,12 +96,8 @@ std::vector<Tensor> norm_bwd(const Tensor& dy, const Tensor& s, const Tensor& w,
   TORCH_CHECK(!has_bias || acc == db_acc.has_value(), "norm_bwd: dw_acc and db_acc must be given together");
   bool gf32 = false;
   if (acc) {
-    gf32 = check_grad(*dw_acc, "dw_acc");
-    TORCH_CHECK(dw_acc->numel() == C && dw_acc->is_contiguous(), "dw_acc shape");
-    if (has_bias) {
-      TORCH_CHECK(check_grad(*db_acc, "db_acc") == gf32, "db_acc dtype must match dw_acc");
-      TORCH_CHECK(db_acc->numel() == C && db_acc->is_contiguous(), "db_acc shape");
-    }
+    gf32 = check_grad(*dw_acc, C, "dw_acc");
+    if (has_bias) TORCH_CHECK(check_grad(*db_acc, C, "db_acc") == gf32, "db_acc dtype must match dw_acc");
   } else {
     TORCH_CHECK(w.scalar_type() == at::kBFloat16, "norm_bwd: bf16 weight");
   }
@@ -112,8 +110,7 @@ std::vector<Tensor> norm_bwd(const Tensor& dy, const Tensor& s, const Tensor& w,
   Tensor dbp = has_bias ? at::empty({G, C}, f32) : Tensor();
   Tensor xbp;
   if (xb_acc) {  // fused bias gradient of the producer of x: accumulated into xb_acc
-    TORCH_CHECK(acc && check_grad(*xb_acc, "xb_acc") == gf32, "xb_acc needs dw_acc targets of the same dtype");
-    TORCH_CHECK(xb_acc->numel() == C && xb_acc->is_contiguous(), "xb_acc shape");
+    TORCH_CHECK(acc && check_grad(*xb_acc, C, "xb_acc") == gf32, "xb_acc needs dw_acc targets of the same dtype");
     xbp = at::empty({G, C}, f32);
   }
   if (N > 0) {
@@ -154,8 +151,7 @@ Tensor bias_grad(const Tensor& dy, const std::optional<Tensor>& out_acc) {
   Tensor out;
   bool of32 = false;
   if (out_acc) {
-    of32 = check_grad(*out_acc, "out_acc");
-    TORCH_CHECK(out_acc->numel() == C && out_acc->is_contiguous(), "out_acc shape");
+    of32 = check_grad(*out_acc, C, "out_acc");
     out = *out_acc;
   } else {
     out = at::zeros({C}, dy.options());
@@ -187,14 +183,12 @@ Tensor wgrad(const Tensor& dy, const Tensor& x, const std::optional<Tensor>& out
   check_aligned16(x, "x");
   bool of32 = false, bf32 = false;
   if (out_acc) {
-    of32 = check_grad(*out_acc, "out_acc");
-    TORCH_CHECK(out_acc->numel() == P * Q && out_acc->is_contiguous(), "wgrad: out_acc shape");
+    of32 = check_grad(*out_acc, P * Q, "wgrad: out_acc");
     check_aligned16(*out_acc, "out_acc");
   }
   if (bias_acc) {
     TORCH_CHECK(out_acc.has_value(), "wgrad: bias_acc needs out_acc");
-    bf32 = check_grad(*bias_acc, "bias_acc");
-    TORCH_CHECK(bias_acc->numel() == P && bias_acc->is_contiguous(), "wgrad: bias_acc [P]");
+    bf32 = check_grad(*bias_acc, P, "wgrad: bias_acc");
     check_aligned16(*bias_acc, "bias_acc");
   }
   const pllm::WgradPlan plan = pllm::wgrad_plan(pllm::gemm_settings(), pllm::gemm_cus(), (int)M, (int)P, (int)Q, of32,
@@ -305,8 +299,7 @@ std::tuple<Tensor, Tensor> gemm_tn(const Tensor& a, const Tensor& b, const std::
   bool of32 = false;
   if (bias_acc) {
     TORCH_CHECK(epi == 3 || epi == 4, "gemm_tn: bias_acc only with epi 3 / 4");
-    of32 = check_grad(*bias_acc, "bias_acc");
-    TORCH_CHECK(bias_acc->numel() == N && bias_acc->is_contiguous(), "gemm_tn: bias_acc [N]");
+    of32 = check_grad(*bias_acc, N, "gemm_tn: bias_acc");
   }
   if (M > 0) {
     pllm::gemm_tn(g, plan, (int)epi, cur_stream());
@@ -437,10 +430,9 @@ Tensor act_bwd_bias(const Tensor& dy, const Tensor& xin, int64_t op, Tensor& bia
   check_bf16(xin, "x");
   check_contig(dy, "dy");
   check_contig(xin, "x");
-  const bool gf32 = check_grad(bias_acc, "bias_acc");
   const int64_t C = dy.size(-1);
+  const bool gf32 = check_grad(bias_acc, C, "bias_acc");
   TORCH_CHECK(dy.sizes() == xin.sizes() && C % 8 == 0, "act_bwd_bias shapes");
-  TORCH_CHECK(bias_acc.numel() == C && bias_acc.is_contiguous(), "bias_acc shape");
   const int64_t N = dy.numel() / C;
   Tensor dx = at::empty_like(dy);
   if (N > 0) {
@@ -594,10 +586,8 @@ std::tuple<Tensor, Tensor> qk_norm_bwd_(Tensor& dqkv, const Tensor& qkv, const T
   TORCH_CHECK(acc == dwk_acc.has_value(), "qk_norm_bwd_: dwq_acc and dwk_acc go together");
   bool gf32 = false;
   if (acc) {
-    gf32 = check_grad(*dwq_acc, "dwq_acc");
-    TORCH_CHECK(check_grad(*dwk_acc, "dwk_acc") == gf32, "dwk_acc dtype must match dwq_acc");
-    TORCH_CHECK(dwq_acc->numel() == D && dwk_acc->numel() == D && dwq_acc->is_contiguous() && dwk_acc->is_contiguous(),
-                "qk_norm_bwd_: accumulate target shape [D]");
+    gf32 = check_grad(*dwq_acc, D, "qk_norm_bwd_: dwq_acc");
+    TORCH_CHECK(check_grad(*dwk_acc, D, "qk_norm_bwd_: dwk_acc") == gf32, "dwk_acc dtype must match dwq_acc");
   }
   Tensor dwq = acc ? *dwq_acc : at::zeros({D}, wq.options());
   Tensor dwk = acc ? *dwk_acc : at::zeros({D}, wk.options());
@@ -631,8 +621,7 @@ Tensor attn_sink_bwd(const Tensor& lse, const Tensor& delta, const Tensor& sinks
   TORCH_CHECK(B * T < (int64_t)1 << 31, "attn_sink_bwd: B * T must be below 2^31");
   bool gf32 = false;
   if (acc) {
-    gf32 = check_grad(*acc, "acc");
-    TORCH_CHECK(acc->numel() == H && acc->is_contiguous(), "attn_sink_bwd: accumulate target shape [", H, "]");
+    gf32 = check_grad(*acc, H, "attn_sink_bwd: acc");
   }
   Tensor out = acc ? *acc : at::zeros({H}, sinks.options());
   if (B * T > 0 && H > 0) {
@@ -883,13 +872,11 @@ std::vector<Tensor> embedding_bwd(const Tensor& dx, const Tensor& idx, int64_t V
   TORCH_CHECK(!has_wpe || acc == dwpe_acc.has_value(), "embedding_bwd: both or neither accumulation targets");
   bool gf32 = false;
   if (acc) {
-    gf32 = check_grad(*dwte_acc, "dwte_acc");
+    gf32 = check_grad(*dwte_acc, V * C, "dwte_acc");
     check_aligned16(*dwte_acc, "dwte_acc");
-    TORCH_CHECK(dwte_acc->numel() == V * C && dwte_acc->is_contiguous(), "dwte_acc shape");
     if (has_wpe) {
-      TORCH_CHECK(check_grad(*dwpe_acc, "dwpe_acc") == gf32, "dwpe_acc dtype must match dwte_acc");
+      TORCH_CHECK(check_grad(*dwpe_acc, n_pos * C, "dwpe_acc") == gf32, "dwpe_acc dtype must match dwte_acc");
       check_aligned16(*dwpe_acc, "dwpe_acc");
-      TORCH_CHECK(dwpe_acc->numel() == n_pos * C && dwpe_acc->is_contiguous(), "dwpe_acc shape");
     }
   }
   TORCH_CHECK(idx.is_cuda(), "idx on GPU");

@@ -77,62 +77,81 @@ def _ops():
 # backward kernels/GEMMs ADD their weight gradients straight into
 # ``p._pllm_gradbuf`` (a view of that buffer, fp32 by default: in-kernel
 # read-add-write epilogues) instead of returning a fresh tensor that autograd's
-# AccumulateGrad would then add in a separate pass.  ``_notify`` tells the
-# data-parallel engine that a contribution landed (it replaces the
-# post-accumulate-grad hook for these).  The engines count the notifications
-# of each parameter, so a writer takes its slot, writes it and notifies if and
-# only if it wrote, else returns a fresh tensor: ``_linear_param_grads``,
-# ``_bias_param_grad`` and ``_bias_grad_by`` below are that sequence for the
-# linear layers' weights and biases.
+# AccumulateGrad would then add in a separate pass.  The data-parallel engines
+# count each parameter's notifications and the optimizer expects a slot's
+# freshness flag consumed once per step, so every writer follows one sequence:
+# ``_take`` the slots its kernel writes (all or none), write, ``_wrote`` -- or,
+# without slots, return fresh tensors and tell nobody.  Nothing else in this
+# package touches a parameter's slot attributes.
 # ---------------------------------------------------------------------------
-def _acc_target(p):
-    """The flat-gradient slot a writer ADDS into.  A slot the optimizer left uncleared (lazy zeroing,
-    ``FlatAdamW(lazy_zero=True)``: it expects an overwriting first write, see ``_set_target``) is
-    zeroed here first, so every accumulating writer stays correct whatever runs first."""
-    if p is None or not getattr(p, "_pllm_flat_grad", False):
+def _slot(p):
+    """``p``'s slot of the flat gradient; None without one or while another writer holds it reserved."""
+    free = getattr(p, "_pllm_flat_grad", False) and not getattr(p, "_pllm_grad_reserved", False)
+    return getattr(p, "_pllm_gradbuf", None) if free else None
+
+
+def _take(*params, whole: bool = False):
+    """The flat-gradient slots of the parameters one kernel writes together, one per parameter (a None entry --
+    the layer has no such parameter -- stays None), all or nothing: when one of them has no slot to give, every
+    entry is None and no flag or buffer has been touched.  A slot the optimizer left uncleared (fresh: lazy
+    zeroing, ``FlatAdamW(lazy_zero=True)``) is zeroed here, so an ADDING writer is right whatever ran first.
+    ``whole``: the writer produces the entire gradient (the weight-gradient GEMM, ``qk_norm_bwd_``,
+    ``attn_sink_bwd``) -> (slots, overwrite): with every slot fresh nothing is zeroed and the kernel stores
+    instead of adding -- no zero fill, no read of zeros; else the fresh ones are zeroed and it adds."""
+    slots, overwrite = tuple(_slot(p) for p in params), False
+    if any(s is None and p is not None for s, p in zip(slots, params)):
+        slots = (None,) * len(params)
+    else:
+        fresh = [p for p in params if getattr(p, "_pllm_grad_fresh", False)]
+        overwrite = whole and len(fresh) == sum(s is not None for s in slots) > 0
+        for p in fresh:
+            p._pllm_grad_fresh = False
+            if not overwrite:
+                p._pllm_gradbuf.zero_()
+    return (slots, overwrite) if whole else slots
+
+
+def _wrote(*params):
+    """Tell the parameters (None entries skipped), in this order, that their slots were written."""
+    for cb in (getattr(p, "_pllm_grad_ready", None) for p in params):
+        if cb is not None:
+            cb()
+
+
+def _reserve(p):
+    """``p``'s slot for a writer that stores the whole gradient now and finishes it in a later call (the LM
+    head: written in its forward, scaled in place in its backward); only a fresh contiguous fp32 slot.  Until
+    ``_release`` every other taker finds no slot and returns a tensor, which autograd's AccumulateGrad hands
+    to the optimizer's hook after the last producer: the in-place scale never covers another writer's part."""
+    buf = _slot(p) if getattr(p, "_pllm_grad_fresh", False) else None
+    if buf is None or buf.dtype != torch.float32 or not buf.is_contiguous():
         return None
-    buf = getattr(p, "_pllm_gradbuf", None)
-    if buf is not None and getattr(p, "_pllm_grad_fresh", False):
-        p._pllm_grad_fresh = False
-        buf.zero_()
+    p._pllm_grad_fresh, p._pllm_grad_reserved = False, True
     return buf
 
 
-def _set_target(p):
-    """(slot, overwrite) for a writer that produces a weight's whole gradient at once (the weight-
-    gradient GEMMs): when the optimizer left the slot uncleared this step, the writer stores instead of
-    adding -- no zero fill and no read of zeros (train/optim.py lazy zeroing)."""
-    if p is None or not getattr(p, "_pllm_flat_grad", False):
-        return None, False
-    buf = getattr(p, "_pllm_gradbuf", None)
-    fresh = buf is not None and getattr(p, "_pllm_grad_fresh", False)
-    if fresh:
-        p._pllm_grad_fresh = False
-    return buf, fresh
-
-
-def _notify(p):
-    cb = getattr(p, "_pllm_grad_ready", None)
-    if cb is not None:
-        cb()
+def _release(p):
+    """End ``p``'s reservation -> its slot."""
+    p._pllm_grad_reserved = False
+    return p._pllm_gradbuf
 
 
 def _linear_param_grads(dy2, x2, w, b, need_w: bool = True, need_b: bool = True, fuse_bias: bool = True):
     """(dw, db) of y = x W^T + b from dy2 [rows, N] and x2 [rows, K]: each goes into its parameter's flat-gradient
     slot (None is returned for it and the parameter is notified, weight before bias) or comes back as a fresh
-    tensor.  The weight-gradient GEMM writes the whole of dW (``_set_target``); with ``fuse_bias`` the bias
+    tensor.  The weight-gradient GEMM writes the whole of dW (``_take(w, whole=True)``); with ``fuse_bias`` the bias
     gradient rides along it when both have slots (FUSED_WGRAD_BIAS), else it is a ``bias_grad`` pass of its own."""
     dw = db = None
     need_b = need_b and b is not None
     if need_w:
-        tgt, fresh = _set_target(w)
+        (tgt,), fresh = _take(w, whole=True)
         # (no weight slot: no fused bias target either, the bias takes the separate pass below)
-        btgt = _acc_target(b) if need_b and fuse_bias and tgt is not None and FUSED_WGRAD_BIAS else None
+        (btgt,) = _take(b) if need_b and fuse_bias and tgt is not None and FUSED_WGRAD_BIAS else (None,)
         dw = _weight_grad(dy2, x2, tgt, btgt, overwrite=fresh)
         if tgt is not None:
-            _notify(w)
+            _wrote(w)
         if btgt is not None:
-            _notify(b)
+            _wrote(b)
             need_b = False
     if need_b:
         db = _bias_param_grad(dy2, b)
@@ -141,23 +160,23 @@ def _linear_param_grads(dy2, x2, w, b, need_w: bool = True, need_b: bool = True,
 
 def _bias_param_grad(dy2, b):
     """Column sums of dy2 added into ``b``'s flat-gradient slot (-> None, ``b`` notified), else returned."""
-    tgt = _acc_target(b)
+    (tgt,) = _take(b)
     if tgt is None:
         return _ops().bias_grad(dy2.contiguous())
     _ops().bias_grad(dy2.contiguous(), tgt)
-    _notify(b)
+    _wrote(b)
     return None
 
 
 def _bias_grad_by(b, run):
     """(run(acc), db) for a kernel ``run`` that adds ``b``'s gradient into ``acc`` beside its own work (a GEMM
     epilogue's column sums): ``acc`` is b's flat-gradient slot (db None, ``b`` notified) or fresh fp32 zeros."""
-    tgt = _acc_target(b)
+    (tgt,) = _take(b)
     acc = tgt if tgt is not None else torch.zeros(b.shape[0], device=b.device, dtype=torch.float32)
     out = run(acc)
     if tgt is None:
         return out, acc.to(b.dtype)
-    _notify(b)
+    _wrote(b)
     return out, None
 
 
@@ -246,7 +265,7 @@ def _dgrad(dy, weight):
 
 def _weight_grad(dy2, x2, tgt, btgt=None, overwrite: bool = False):
     """dW = dy2^T @ x2, added into ``tgt`` (bf16 or fp32) when given (returns None) else returned;
-    ``overwrite``: stored into ``tgt`` instead (its first write of the step, ``_set_target``).
+    ``overwrite``: stored into ``tgt`` instead (its first write of the step, ``_take(.., whole=True)``).
     ``btgt`` (with ``tgt``): the bias gradient (column sums of dy2) is added into it as well -- on the
     hand-written kernel inside the GEMM (its all-ones MFMAs), else by the bias_grad kernels."""
     hip_ok = dy2.shape[1] % 8 == 0 and x2.shape[1] % 8 == 0 and dy2.shape[0] % 64 == 0
@@ -595,25 +614,17 @@ class _NormFn(torch.autograd.Function):
         C = ctx.shp[-1]
         dy2 = dy.reshape(-1, C).contiguous()
         ds2 = ds.reshape(-1, C).contiguous() if ds is not None else None
-        tw = _acc_target(ctx.w)
-        tb = _acc_target(ctx.b) if ctx.has_bias else None
-        direct = tw is not None and (not ctx.has_bias or tb is not None)
-        txb = _acc_target(ctx.xb) if direct else None  # x_bias rides in the kernel only on its accumulating form
-        dxb = None
-        if direct:
+        # (x_bias rides in the kernel only on its accumulating form: one group, all slots or none)
+        tw, tb, txb = _take(ctx.w, ctx.b, ctx.xb)
+        dw = db = dxb = None
+        if tw is not None:
             outs = (_ops().norm_bwd_acc(dy2, s, weight, mean, rstd, ds2, ctx.has_bias, ctx.rms, tw, tb, txb),)
-            dw = db = None
-            _notify(ctx.w)
-            if ctx.has_bias:
-                _notify(ctx.b)
-            if txb is not None:
-                _notify(ctx.xb)
+            _wrote(ctx.w, ctx.b, ctx.xb)
         else:
             outs = _ops().norm_bwd(dy2, s, weight, mean, rstd, ds2, ctx.has_bias, ctx.rms)
-            dw = outs[1]
-            db = outs[2] if ctx.has_bias else None
-        if ctx.xb is not None and txb is None:  # the column sums of dx as a pass of their own
-            dxb = _bias_param_grad(outs[0], ctx.xb)
+            dw, db = outs[1], (outs[2] if ctx.has_bias else None)
+            if ctx.xb is not None:  # the column sums of dx as a pass of their own
+                dxb = _bias_param_grad(outs[0], ctx.xb)
         ctx.w = ctx.b = ctx.xb = None
         dx = outs[0].view(ctx.shp)
         return dx, (dx if ctx.has_res else None), dw, db, None, None, dxb
@@ -751,17 +762,11 @@ def _attn_packed_fwd(qkv, H, Hkv, causal, scale, cos, sin, qkn=None, kv_start=No
 def _qk_norm_bwd(dqkv, qkv, rstd, wq, wk, H, Hkv):
     """QK-norm backward in place on the q / k columns of ``dqkv`` -> (dwq, dwk): None when the gain
     gradients went straight into the flat-gradient slots, else fresh tensors."""
-    (tq, fq), (tk, fk) = _set_target(wq), _set_target(wk)
-    if tq is None or tk is None:
-        for p, t, f in ((wq, tq, fq), (wk, tk, fk)):
-            if t is not None and f:  # not written here after all: leave the slot as it was found
-                p._pllm_grad_fresh = True
-        return _ops().qk_norm_bwd_(dqkv, qkv, rstd, wq, wk, H, Hkv, None, None, False)
-    if fq != fk:  # one slot already written this step: zero the other and add into both
-        (tq if fq else tk).zero_()
-    _ops().qk_norm_bwd_(dqkv, qkv, rstd, wq, wk, H, Hkv, tq, tk, fq and fk)
-    _notify(wq)
-    _notify(wk)
+    (tq, tk), overwrite = _take(wq, wk, whole=True)
+    out = _ops().qk_norm_bwd_(dqkv, qkv, rstd, wq, wk, H, Hkv, tq, tk, overwrite)
+    if tq is None:
+        return out
+    _wrote(wq, wk)
     return None, None
 
 
@@ -772,13 +777,12 @@ def _sinks_kw(sinks) -> dict:
 
 def _sink_bwd(lse, delta, sinks):
     """Gradient of the attention sinks, ds[h] = -sum_{b,i} exp(s[h] - lse[b,h,i]) delta[b,h,i] (csrc/attn_sink.hip):
-    None when it went straight into the flat-gradient slot (the whole gradient at once: ``_set_target``), else
-    a fresh tensor."""
-    tgt, fresh = _set_target(sinks)
+    None when it went straight into the flat-gradient slot (the whole gradient at once), else a fresh tensor."""
+    (tgt,), overwrite = _take(sinks, whole=True)
+    out = _ops().attn_sink_bwd(lse, delta, sinks, tgt, overwrite)
     if tgt is None:
-        return _ops().attn_sink_bwd(lse, delta, sinks, None, False)
-    _ops().attn_sink_bwd(lse, delta, sinks, tgt, fresh)
-    _notify(sinks)
+        return out
+    _wrote(sinks)
     return None
 
 
@@ -1142,10 +1146,10 @@ class _ActFn(torch.autograd.Function):
         b, ctx.b = ctx.b, None
         if b is None:
             return _ops().act_bwd(dy, t, ctx.kind), None, None
-        tgt = _acc_target(b)  # (not _bias_grad_by: without a slot it is another kernel pair, not fresh zeros)
+        (tgt,) = _take(b)  # (not _bias_grad_by: without a slot it is another kernel pair, not fresh zeros)
         if tgt is not None:
             dx = _ops().act_bwd_bias(dy, t, ctx.kind, tgt)
-            _notify(b)
+            _wrote(b)
             return dx, None, None
         dx = _ops().act_bwd(dy, t, ctx.kind)
         return dx, _ops().bias_grad(dx), None
@@ -1200,16 +1204,13 @@ class _EmbeddingFn(torch.autograd.Function):
     def backward(ctx, dx):
         (idx,) = ctx.saved_tensors
         has_pos = ctx.n_pos > 0
-        tt = _acc_target(ctx.wte)
-        tp = _acc_target(ctx.wpe) if has_pos else None
-        if tt is not None and (not has_pos or tp is not None):
-            _ops().embedding_bwd_acc(dx.contiguous(), idx, ctx.V, ctx.n_pos, has_pos, tt, tp)
-            _notify(ctx.wte)
-            if has_pos:
-                _notify(ctx.wpe)
-            ctx.wte = ctx.wpe = None
-            return None, None, None
+        wte, wpe = ctx.wte, ctx.wpe
         ctx.wte = ctx.wpe = None
+        tt, tp = _take(wte, wpe)
+        if tt is not None:
+            _ops().embedding_bwd_acc(dx.contiguous(), idx, ctx.V, ctx.n_pos, has_pos, tt, tp)
+            _wrote(wte, wpe)
+            return None, None, None
         outs = _ops().embedding_bwd(dx.contiguous(), idx, ctx.V, ctx.n_pos, has_pos)
         return None, outs[0], (outs[1] if has_pos else None)
 
@@ -1290,6 +1291,20 @@ def _z_term(lse, z_loss, inv_n, z_out):
         z_out.copy_((lse.square().sum() * inv_n * z_loss).reshape(1))
 
 
+def _scaled_param_grad(p, t, g, dtype, whole: bool = False):
+    """g * t (``t``: the fp32 gradient the forward left) into ``p``'s slot (-> None, ``p`` notified; ``whole``: stored
+    over a fresh slot), else returned as ``dtype``."""
+    (tgt,), overwrite = _take(p, whole=True) if whole else (_take(p), False)
+    if tgt is None:
+        return t.mul_(g).to(dtype)
+    if overwrite:
+        torch.mul(t.view(-1), g, out=tgt.view(-1))
+    else:
+        tgt.view(-1).addcmul_(t.view(-1), g)
+    _wrote(p)
+    return None
+
+
 class _LMHeadCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, weight, bias, targets, ignore_index, z_loss=0.0, cap=None, z_out=None):
@@ -1308,12 +1323,9 @@ class _LMHeadCEFn(torch.autograd.Function):
         # overwrites) the chunks write straight into that slot and the backward only scales it in place by
         # the upstream gradient -- a no-op launch when that is 1 -- instead of a 154 MB fp32 buffer copied and
         # scaled into the slot (GPT-2 small: ~55 us per step).  A slot already holding gradient (accumulation
-        # micro-steps) keeps the separate buffer: the scale applies to this micro-step's part only.
-        direct = None
-        if need_w:
-            tgt, fresh = _set_target(weight)
-            if tgt is not None and fresh and tgt.dtype == torch.float32 and tgt.is_contiguous():
-                direct = tgt
+        # micro-steps) keeps the separate buffer, and a taken one stays reserved until the backward (_reserve):
+        # the scale applies to this call's part only.
+        direct = _reserve(weight) if need_w else None
         dw = (direct.view(V, C) if direct is not None else
               torch.empty(V, C, dtype=torch.float32, device=h.device)) if need_w else None
         db = torch.zeros(V, dtype=torch.float32, device=h.device) if need_b else None
@@ -1353,26 +1365,12 @@ class _LMHeadCEFn(torch.autograd.Function):
                 gh = dh.mul_(g.to(dh.dtype))
         gw = gb = None
         if ctx.direct:  # the weight gradient is already in its flat slot: scale it there (no-op when g == 1)
-            slot = getattr(ctx.w, "_pllm_gradbuf")
-            _ops().scale_(slot.view(-1), g.reshape(1))
-            _notify(ctx.w)
+            _ops().scale_(_release(ctx.w).view(-1), g.reshape(1))
+            _wrote(ctx.w)
         elif dw is not None:
-            tgt, fresh = _set_target(ctx.w)
-            if tgt is not None:
-                if fresh:
-                    torch.mul(dw.view(-1), g, out=tgt.view(-1))
-                else:
-                    tgt.view(-1).addcmul_(dw.view(-1), g)
-                _notify(ctx.w)
-            else:
-                gw = dw.mul_(g).to(ctx.wdtype)
+            gw = _scaled_param_grad(ctx.w, dw, g, ctx.wdtype, whole=True)
         if db is not None:  # (the forward's column sums scaled by g, not a bias_grad pass: no _bias_param_grad)
-            tgt = _acc_target(ctx.b)
-            if tgt is not None:
-                tgt.addcmul_(db, g)
-                _notify(ctx.b)
-            else:
-                gb = db.mul_(g).to(ctx.wdtype)
+            gb = _scaled_param_grad(ctx.b, db, g, ctx.wdtype)
         ctx.w = ctx.b = None
         return gh, gw, gb, None, None, None, None, None
 

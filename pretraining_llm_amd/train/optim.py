@@ -15,7 +15,7 @@ MI355X-first layout instead:
   fp32 ``.grad``, fp32 DDP all-reduce: scripts/train_transformer.py:66-69,122-126),
   micro-step accumulation, the tied embedding's two gradient pieces and the DP sum
   are all kept in fp32.  The backward kernels add straight into that buffer
-  (``p._pllm_gradbuf``, see ops._acc_target); where grad and param dtypes agree it is
+  (``p._pllm_gradbuf``, see ops._take); where grad and param dtypes agree it is
   also ``p.grad``, otherwise (bf16 params, fp32 grads -- torch forbids a ``.grad``
   of another dtype) any gradient autograd still produces is folded into the buffer
   by a post-accumulate hook and released;
@@ -100,7 +100,7 @@ class FlatAdamW:
             seg.copy_(p.data)
             p.data = seg
             p._pllm_gradbuf = self.flat_grad[o:o + p.numel()].view_as(p)
-            p._pllm_flat_grad = True  # backward kernels add straight into p._pllm_gradbuf (ops._acc_target)
+            p._pllm_flat_grad = True  # backward kernels add straight into p._pllm_gradbuf (ops._take)
             if self.grad_is_param_grad:
                 p.grad = p._pllm_gradbuf
             else:
@@ -149,8 +149,8 @@ class FlatAdamW:
         # Lazy zeroing (HIP path): zero_grad clears only the slots that accumulating writers fill (norms,
         # biases, embedding tables) in one launch, and marks the weight-GEMM slots "fresh": their first
         # writer of the step -- the weight-gradient GEMM, which produces the whole gradient at once --
-        # stores instead of adding (ops._set_target), so those slots are never zero-filled nor read back
-        # as zeros.  Any other writer zeroes a fresh slot before adding (ops._acc_target); a slot no
+        # stores instead of adding (ops._take with ``whole``), so those slots are never zero-filled nor read
+        # back as zeros.  Any other writer zeroes a fresh slot before adding (ops._take); a slot no
         # writer touched is zeroed before the step reads it (_clear_unwritten).
         if lazy_zero is None:
             lazy_zero = _ab("lazy_zero", True)
@@ -172,12 +172,14 @@ class FlatAdamW:
         """Fresh slots no writer touched this step (an unused weight) hold last step's gradient: zero them.
         ``idx``: only these parameter indices (a DP bucket about to be all-reduced: a stale slot must be
         zeroed BEFORE it enters the sum, or a weight unused on some ranks only would add last step's
-        gradient into every replica -- parallel/dp.py DataParallel._launch)."""
+        gradient into every replica -- parallel/dp.py DataParallel._launch).  A slot still reserved
+        (ops._reserve: an LM-head forward under grad mode whose backward never ran) holds an unscaled partial
+        gradient nobody finished: unwritten as well, and released."""
         if self.lazy_zero:
             params = self._fresh_params if idx is None else [self.params[i] for i in idx]
             for p in params:
-                if getattr(p, "_pllm_grad_fresh", False):
-                    p._pllm_grad_fresh = False
+                if getattr(p, "_pllm_grad_fresh", False) or getattr(p, "_pllm_grad_reserved", False):
+                    p._pllm_grad_fresh = p._pllm_grad_reserved = False
                     p._pllm_gradbuf.zero_()
 
     @torch.no_grad()
@@ -203,6 +205,7 @@ class FlatAdamW:
             _lib.require().zero_ranges_(self.flat_grad, self._zero_runs, self._zero_len)
             for p in self._fresh_params:
                 p._pllm_grad_fresh = True
+                p._pllm_grad_reserved = False  # (a forward whose backward never ran: ops._reserve)
         else:
             self.flat_grad.zero_()
         for i, p in enumerate(self.params):

@@ -1,8 +1,11 @@
-"""The flat-gradient helpers of ops (``_linear_param_grads``, ``_bias_param_grad``, ``_bias_grad_by``,
-``_shadow`` / ``_shadow_or_t``) driven directly on the CPU: parameters dressed by hand the way FlatAdamW and the
-data-parallel engine dress them, the two kernels behind them (``wgrad``, ``bias_grad``) replaced by torch
-stand-ins that also record how they were called.  All values are small integers, so every sum is exact in bf16
-and fp32 alike and the slots are compared with ``torch.equal``."""
+"""The flat-gradient helpers of ops (the slot protocol itself: ``_take`` / ``_wrote`` / ``_reserve`` / ``_release``;
+``_linear_param_grads``, ``_bias_param_grad``, ``_bias_grad_by``, ``_qk_norm_bwd``, ``_sink_bwd``; ``_shadow`` /
+``_shadow_or_t``) driven directly on the CPU: parameters dressed by hand the way FlatAdamW and the data-parallel
+engine dress them, the kernels behind them (``wgrad``, ``bias_grad``, ``qk_norm_bwd_``, ``attn_sink_bwd``) replaced
+by torch stand-ins that also record how they were called.  All values are small integers, so every sum is exact in
+bf16 and fp32 alike and the slots are compared with ``torch.equal``."""
+import itertools
+
 import pytest
 import torch
 import torch.nn as nn
@@ -37,6 +40,29 @@ class _Kernels:
             return s.to(dy.dtype)
         out_acc.add_(s.to(out_acc.dtype))
         return out_acc
+
+    # the two whole-gradient reductions of the attention path.  Stand-in math: the q / k gain gradients are the column
+    # sums of the two halves of dqkv, the sink gradient is minus the column sums of delta
+    def qk_norm_bwd_(self, dqkv, qkv, rstd, wq, wk, H, Hkv, acc_q, acc_k, overwrite):
+        self.calls.append(("qk_norm_bwd_", overwrite))
+        assert (acc_q is None) == (acc_k is None)
+        D = wq.shape[0]
+        gq, gk = dqkv[:, :D].float().sum(0), dqkv[:, D:].float().sum(0)
+        if acc_q is None:
+            assert overwrite is False
+            return gq.to(wq.dtype), gk.to(wk.dtype)
+        for acc, g in ((acc_q, gq), (acc_k, gk)):
+            acc.copy_(g) if overwrite else acc.add_(g.to(acc.dtype))
+        return acc_q, acc_k
+
+    def attn_sink_bwd(self, lse, delta, sinks, acc, overwrite):
+        self.calls.append(("attn_sink_bwd", overwrite))
+        g = -delta.float().sum(0)
+        if acc is None:
+            assert overwrite is False
+            return g.to(sinks.dtype)
+        acc.copy_(g) if overwrite else acc.add_(g.to(acc.dtype))
+        return acc
 
 
 @pytest.fixture
@@ -150,6 +176,140 @@ def test_bias_writers(kernels, slot, fresh):
         else:
             assert db is None and log == ["b"] and b._pllm_grad_fresh is False
             assert torch.equal(b._pllm_gradbuf.float(), b_old.float() + dy.float().sum(0))
+
+
+def _same(a, b):
+    """Bitwise-equal contents, NaNs included."""
+    return torch.equal(a.isnan(), b.isnan()) and torch.equal(a.nan_to_num(), b.nan_to_num())
+
+
+# a group member: no such parameter (None entry), a parameter without a slot, or (slot dtype, fresh)
+_MEMBERS = ["absent", "noslot", (torch.float32, True), (torch.float32, False), (torch.bfloat16, True),
+            (torch.bfloat16, False)]
+
+
+@pytest.mark.parametrize("whole", [False, True])
+@pytest.mark.parametrize("size", [1, 2, 3])
+def test_take_groups(size, whole):
+    """``_take`` over every group of ``size`` members: all slots or none, and on "none" nothing is touched -- not a
+    flag, not a buffer (the fresh ones keep their NaNs).  An adding group zeroes exactly its fresh members; a
+    ``whole`` group overwrites only when every member is fresh, else it zeroes the fresh ones.  Nobody is notified."""
+    torch.manual_seed(size)
+    for kinds in itertools.product(_MEMBERS, repeat=size):
+        log, params, olds = [], [], []
+        for i, kind in enumerate(kinds):
+            p, old = (None, None) if kind == "absent" else _param((N,), *((None, False) if kind == "noslot" else kind),
+                                                                  log, str(i))
+            params.append(p)
+            olds.append(old)
+        before = [None if getattr(p, "_pllm_gradbuf", None) is None else p._pllm_gradbuf.clone() for p in params]
+        out = ops._take(*params, whole=whole)
+        slots, overwrite = out if whole else (out, False)
+        assert isinstance(slots, tuple) and len(slots) == size and log == []
+        present = [k for k in kinds if k != "absent"]
+        if not present or "noslot" in present:  # incomplete: no slots, everything as it was found
+            assert slots == (None,) * size and overwrite is False
+            for p, kind, b in zip(params, kinds, before):
+                if b is not None:
+                    assert p._pllm_grad_fresh is kind[1] and _same(p._pllm_gradbuf, b)
+            continue
+        assert overwrite is (whole and all(k[1] for k in present))
+        for p, kind, slot, b, old in zip(params, kinds, slots, before, olds):
+            if p is None:
+                assert slot is None
+                continue
+            assert slot is p._pllm_gradbuf and p._pllm_grad_fresh is False
+            if kind[1] and overwrite:  # left for the kernel to store over
+                assert _same(slot, b)
+            else:  # a fresh slot zeroed, a written one kept
+                assert torch.equal(slot, old)
+
+
+def test_wrote_order():
+    log = []
+    a, b = _param((N,), torch.float32, False, log, "a")[0], _param((N,), None, False, log, "b")[0]
+    ops._wrote(a, None, b, a)
+    assert log == ["a", "b", "a"]
+    ops._wrote(nn.Parameter(_ints(N)), None)  # nobody listens
+
+
+def test_reservation():
+    """A reserved slot (the LM head between its forward and its backward) is no slot to anyone else, alone or in
+    a group, and nothing of the group is touched; releasing gives it back as a written slot."""
+    log = []
+    p, _ = _param((N, K), torch.float32, True, log, "p")
+    q, _ = _param((N,), torch.float32, True, log, "q")
+    buf = ops._reserve(p)
+    assert buf is p._pllm_gradbuf and p._pllm_grad_fresh is False and torch.isnan(buf).all()  # its to store over
+    assert ops._reserve(p) is None
+    assert ops._take(p) == (None,) and ops._take(p, whole=True) == ((None,), False)
+    assert ops._take(q, p) == (None, None) and ops._take(None, p, q, whole=True) == ((None, None, None), False)
+    assert q._pllm_grad_fresh is True and torch.isnan(q._pllm_gradbuf).all()
+    assert p._pllm_grad_fresh is False and torch.isnan(buf).all() and log == []
+    buf.fill_(2.0)  # the reserving writer's part
+    assert ops._release(p) is buf
+    (got,), overwrite = ops._take(p, whole=True)
+    assert got is buf and overwrite is False and torch.equal(buf, torch.full((N, K), 2.0))
+    (gq, gp) = ops._take(q, p)
+    assert gq is q._pllm_gradbuf and gp is buf and torch.equal(gq, torch.zeros(N)) and q._pllm_grad_fresh is False
+    # only a fresh fp32 slot can be reserved; a refusal touches nothing
+    for dtype, fresh in [(torch.float32, False), (torch.bfloat16, True), (None, False)]:
+        r, _ = _param((N, K), dtype, fresh, log, "r")
+        b0 = None if dtype is None else r._pllm_gradbuf.clone()
+        assert ops._reserve(r) is None
+        if dtype is not None:
+            assert r._pllm_grad_fresh is fresh and _same(r._pllm_gradbuf, b0)
+            assert ops._take(r)[0] is r._pllm_gradbuf  # and it is still there to take
+
+
+_QK_CASES = [((torch.float32, True), (torch.float32, True)), ((torch.float32, True), (torch.float32, False)),
+             ((torch.float32, False), (torch.float32, True)), ((torch.float32, False), (torch.float32, False)),
+             ((torch.bfloat16, True), (torch.bfloat16, False)), ((None, False), (None, False)),
+             ((torch.float32, True), (None, False)), ((None, False), (torch.float32, True))]
+
+
+@pytest.mark.parametrize("q_kind,k_kind", _QK_CASES)
+def test_qk_norm_bwd_slots(kernels, q_kind, k_kind):
+    """The two gain gradients go into their slots together or come back together: stored when both slots are
+    fresh, added otherwise (a fresh one zeroed first), ``wq`` notified before ``wk``; with a slot missing both
+    come back as tensors, nobody is notified and the other slot stays as it was found, flag included."""
+    torch.manual_seed(3)
+    log, D = [], 8
+    dqkv = _ints(32, 2 * D)
+    wq, q_old = _param((D,), *q_kind, log, "wq")
+    wk, k_old = _param((D,), *k_kind, log, "wk")
+    before = [None if old is None else p._pllm_gradbuf.clone() for p, old in ((wq, q_old), (wk, k_old))]
+    gq, gk = dqkv[:, :D].float().sum(0), dqkv[:, D:].float().sum(0)
+    dwq, dwk = ops._qk_norm_bwd(dqkv, dqkv, None, wq, wk, 1, 1)
+    if q_old is None or k_old is None:
+        assert torch.equal(dwq.float(), gq) and torch.equal(dwk.float(), gk) and log == []
+        assert kernels.calls == [("qk_norm_bwd_", False)]
+        for p, kind, b in ((wq, q_kind, before[0]), (wk, k_kind, before[1])):
+            if b is not None:
+                assert p._pllm_grad_fresh is kind[1] and _same(p._pllm_gradbuf, b)
+        return
+    assert dwq is None and dwk is None and log == ["wq", "wk"]
+    assert kernels.calls == [("qk_norm_bwd_", q_kind[1] and k_kind[1])]
+    assert wq._pllm_grad_fresh is False and wk._pllm_grad_fresh is False
+    assert torch.equal(wq._pllm_gradbuf.float(), q_old.float() + gq)
+    assert torch.equal(wk._pllm_gradbuf.float(), k_old.float() + gk)
+
+
+@pytest.mark.parametrize("slot,fresh", [(torch.float32, True), (torch.float32, False), (torch.bfloat16, False),
+                                        (None, False)])
+def test_sink_bwd_slot(kernels, slot, fresh):
+    torch.manual_seed(4)
+    log, H = [], 4
+    delta = _ints(32, H)
+    s, old = _param((H,), slot, fresh, log, "sinks")
+    ds = ops._sink_bwd(None, delta, s)
+    g = -delta.float().sum(0)
+    assert kernels.calls == [("attn_sink_bwd", fresh)]
+    if slot is None:
+        assert torch.equal(ds.float(), g) and log == []
+    else:
+        assert ds is None and log == ["sinks"] and s._pllm_grad_fresh is False
+        assert torch.equal(s._pllm_gradbuf.float(), old.float() + g)
 
 
 def test_shadow_lookup():

@@ -1,6 +1,6 @@
-"""The flat-gradient write protocol of the autograd functions in ops, end to end on four small models: every
-backward takes its parameter's slot of the optimizer's flat gradient (``ops._set_target`` / ``_acc_target``),
-writes it, and notifies the parameter exactly when it wrote.  parallel/dp.py and parallel/zero.py count those
+"""The flat-gradient write protocol of the autograd functions in ops, end to end on five small models: every
+backward takes its parameters' slots of the optimizer's flat gradient (``ops._take``), writes them, and notifies
+the parameters (``ops._wrote``) exactly when it wrote.  parallel/dp.py and parallel/zero.py count those
 notifications per parameter to launch their buckets and train/optim.py expects ``_pllm_grad_fresh`` consumed
 once per slot per step, so the SEQUENCE of notified parameters is part of the contract: it is pinned here as
 literal lists (recorded before the helpers of ops were factored out, they do not come from the code under
@@ -27,6 +27,8 @@ def _cfg(name):
         return get_preset("gpt2-tiny").replace(vocab_size=512, context_length=T, n_embed=128, n_head=2, n_blocks=2)
     if name == "ref":  # ReLU through gemm_lt, no W_o, biased untied head (the CE bias arm)
         return get_preset("ref-small").replace(vocab_size=512, context_length=T, n_embed=128, n_head=2, n_blocks=2)
+    if name == "llama-sinks":  # attention sinks (their gradient: one reduction, _sink_bwd), local and global layers
+        return get_preset("llama-tiny-sinks")
     return get_preset("llama-tiny-qknorm")  # fused SwiGLU, _FlashAttnPacked with RoPE and QK-norm, GQA
 
 
@@ -74,6 +76,15 @@ EXPECTED = {
         "attn_blocks.0.attn.proj.weight", "attn_blocks.0.attn.qkv.weight", "attn_blocks.0.attn.qkv.bias",
         "attn_blocks.0.ln1.weight", "attn_blocks.0.ln1.bias", "token_embed.weight", "position_embed.weight",
     ],
+    # (recorded at the commit before ``_take``, from the NOTIFIED line below)
+    "llama-sinks": [
+        "lm_head.weight", "layer_norm.weight", "attn_blocks.1.mlp.proj.weight", "attn_blocks.1.mlp.hidden.weight",
+        "attn_blocks.1.ln2.weight", "attn_blocks.1.attn.proj.weight", "attn_blocks.1.attn.sinks",
+        "attn_blocks.1.attn.qkv.weight", "attn_blocks.1.ln1.weight", "attn_blocks.0.mlp.proj.weight",
+        "attn_blocks.0.mlp.hidden.weight", "attn_blocks.0.ln2.weight", "attn_blocks.0.attn.proj.weight",
+        "attn_blocks.0.attn.sinks", "attn_blocks.0.attn.qkv.weight", "attn_blocks.0.ln1.weight",
+        "token_embed.weight",
+    ],
 }
 
 
@@ -108,7 +119,7 @@ def _run(name, monkeypatch):
     return notified, fresh, opt.flat_grad.clone()
 
 
-@pytest.mark.parametrize("name", ["gpt2", "ref", "llama-qknorm", "gpt2-unfused"])
+@pytest.mark.parametrize("name", ["gpt2", "ref", "llama-qknorm", "gpt2-unfused", "llama-sinks"])
 def test_notifications_freshness_and_bits(name, monkeypatch):
     notified, fresh, flat = _run(name, monkeypatch)
     print(f"NOTIFIED {name} {notified!r}")  # (shown on failure, or with -s: how EXPECTED was recorded)

@@ -947,6 +947,62 @@ def test_lm_head_ce_chunked(chunk, with_bias, monkeypatch):
         assert _rel(W._pllm_gradbuf.double(), 2 * up * Wf.grad.double()) < 3e-2
 
 
+def test_lm_head_ce_two_calls_on_one_weight():
+    """3 ce(h1, t1) + 0.5 ce(h2, t2) on one weight whose slot is fresh: the first call writes dW1 into the slot
+    in its forward and keeps it reserved, the second call's backward (it runs first) finds no slot and returns
+    0.5 dW2 as a tensor, the first call's backward scales the slot by 3, releases it and notifies, and the
+    optimizer's post-accumulate hook folds the tensor in last: 3 dW1 + 0.5 dW2.  Scaling after the second call had
+    added into the slot would give 3 (dW1 + 0.5 dW2), off by |dW2| / |3 dW1 + 0.5 dW2|: 0.32-0.33 in the fp32
+    reference on the CPU for independent inputs of these sizes (|dW2| / |dW1| = 0.98-1.00), ten times the bound.
+    Then the stale reservation: a forward under grad mode whose backward never runs leaves the slot reserved, and
+    FlatAdamW's _clear_unwritten (zeroed, written) and zero_grad (fresh) both end that."""
+    import torch.nn as nn
+    from pretraining_llm_amd import ops
+    from pretraining_llm_amd.train.optim import FlatAdamW, _fold_grad
+    torch.manual_seed(29)
+    N, C, V = 128, 64, 512
+    W = (torch.randn(V, C, device=DEV) * 0.05).bfloat16().requires_grad_()
+    hs = [(torch.randn(N, C, device=DEV) * 0.5).bfloat16().requires_grad_() for _ in range(2)]
+    ts = [torch.randint(0, V, (N,), device=DEV) for _ in range(2)]
+    dws = []
+    for h, t in zip(hs, ts):  # fp32 torch gradient of each call alone
+        Wf = W.detach().float().requires_grad_()
+        F.cross_entropy(h.detach().float() @ Wf.t(), t).backward()
+        dws.append(Wf.grad.double())
+    want, wrong = 3 * dws[0] + 0.5 * dws[1], 3 * (dws[0] + 0.5 * dws[1])
+    assert _rel(wrong, want) > 0.3  # the inputs tell the two apart
+    log = []
+    W._pllm_grad_ready = lambda: log.append("W")
+    W._pllm_flat_grad = True
+    W._pllm_gradbuf = torch.full((V, C), float("nan"), device=DEV)
+    W._pllm_grad_fresh = True
+    W.register_post_accumulate_grad_hook(_fold_grad)  # as FlatAdamW does for fp32 slots of bf16 parameters
+    ce = [ops.lm_head_cross_entropy(h, W, None, t) for h, t in zip(hs, ts)]
+    loss = 3.0 * ce[0] + 0.5 * ce[1]
+    assert W._pllm_grad_reserved is True and W._pllm_grad_fresh is False
+    loss.backward()
+    err = _rel(W._pllm_gradbuf.double(), want)
+    print(f"two calls: rel err {err:.3e} (the wrong order would give {_rel(wrong, want):.3f})")
+    assert err < 3e-2
+    assert W._pllm_grad_reserved is False and W._pllm_grad_fresh is False and W.grad is None
+    assert log == ["W"]  # the slot's one direct write; the folded part is the hook's to report
+    # a forward that never gets its backward
+    model = nn.Sequential(nn.Linear(C, C, bias=False), nn.Linear(C, V, bias=False))
+    model = model.to(device=DEV, dtype=torch.bfloat16)
+    opt = FlatAdamW(model, lr=1e-3, lazy_zero=True)
+    Wm = model[1].weight
+    assert opt.lazy_zero and Wm._pllm_grad_fresh is True
+    for end in (opt._clear_unwritten, opt.zero_grad):
+        ops.lm_head_cross_entropy(hs[0], Wm, None, ts[0])
+        assert Wm._pllm_grad_reserved is True and Wm._pllm_grad_fresh is False
+        assert ops._take(Wm) == (None,)
+        end()
+        assert Wm._pllm_grad_reserved is False
+        assert Wm._pllm_grad_fresh is True or (Wm._pllm_gradbuf == 0).all()  # fresh, or zero and written
+        assert ops._take(Wm, whole=True)[0][0] is Wm._pllm_gradbuf
+        opt.zero_grad()
+
+
 @pytest.mark.parametrize("D,T,H,Hkv,B", [(32, 1024, 4, 4, 2), (64, 2048, 4, 2, 1), (64, 4096, 2, 2, 1),
                                          (128, 2048, 4, 1, 1), (128, 4096, 2, 2, 1), (64, 1000, 4, 4, 2)])
 def test_attention_bwd_long_sequences(D, T, H, Hkv, B):

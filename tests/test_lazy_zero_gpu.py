@@ -1,4 +1,4 @@
-"""Lazy gradient zeroing (train/optim.py FlatAdamW(lazy_zero=True), ops._set_target / _acc_target): zero_grad
+"""Lazy gradient zeroing (train/optim.py FlatAdamW(lazy_zero=True), ops._take): zero_grad
 clears only the accumulate-only slots and the weight-gradient GEMMs overwrite their slots on the first write of
 a step.  The training trajectory must be bit-identical to full zeroing, with gradient accumulation, in the
 captured (hipGraph) step and eagerly, and a weight no writer touched must read as a zero gradient."""
