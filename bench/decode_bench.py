@@ -9,7 +9,9 @@ and 1024, interleaved round by round).  ``--kernels-only`` stops after the kerne
 ``--softcap C`` runs every batch size twice, without and with final-logit soft-capping (``final_logit_softcap=C``:
 elementwise ops on the step's [B, V] logits).  ``--sinks`` runs every batch size without and with attention sinks
 (``attn_sinks=True``: a second model of the same shape, its sinks drawn from N(0, 1)).  ``--model-only`` skips the
-kernel arms.
+kernel arms.  ``--fp8-weights`` runs every batch size with the bf16 weights and with FP8 decode weights
+(``GPT.quantize_decode_weights``: the same model, its projections and head quantised per row), ``--rounds`` times in
+alternation, and reports every round and the medians.
 Prints one JSON line per configuration.
 
 usage: python bench/decode_bench.py [--batches 1,16,64] [--prompt 128] [--new 256] [--kernels-only] [--softcap 30]
@@ -50,6 +52,7 @@ def main():
     ap.add_argument("--softcap", type=float, default=None)
     ap.add_argument("--model-only", action="store_true")
     ap.add_argument("--sinks", action="store_true")
+    ap.add_argument("--fp8-weights", action="store_true")
     args = ap.parse_args()
     import torch
     from pretraining_llm_amd import ops
@@ -105,6 +108,9 @@ def main():
         with torch.no_grad():
             for blk in models[True].attn_blocks:
                 blk.attn.sinks.normal_()
+    if args.fp8_weights:
+        fp8_weights_arm(args, models[False], dev)
+        return
     caps = [None] + ([args.softcap] if args.softcap else [])
     for B, cap, sk in ((int(b), c, s) for b in args.batches.split(",") for c in caps for s in models):
         model, cfg = models[sk], models[sk].config.replace(final_logit_softcap=None)
@@ -127,6 +133,40 @@ def main():
             res[f"{mode}_tok_per_s"] = round(B * args.new / dt, 1)
             res[f"{mode}_ms_per_token_step"] = round(1000 * dt / args.new, 3)
             assert out.shape == (B, args.prompt + args.new)
+        print(json.dumps(res), flush=True)
+
+
+def fp8_weights_arm(args, model, dev):
+    """bf16 against FP8 decode weights on one model, interleaved round by round (round 0 is warm-up)."""
+    import statistics
+    import torch
+    cfg = model.config
+    for B in (int(b) for b in args.batches.split(",")):
+        idx = torch.randint(0, cfg.vocab_size, (B, args.prompt), device=dev)
+        tps = {(w, mode): [] for w in ("bf16", "fp8") for mode in ("eager", "graph")}
+        for rnd in range(args.rounds + 1):
+            for w in ("bf16", "fp8"):
+                if w == "fp8":
+                    model.quantize_decode_weights("fp8")
+                for mode in ("eager", "graph"):
+                    g = mode == "graph"
+                    if rnd == 0:
+                        model.generate(idx, 4, temperature=0.0, cuda_graph=g)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    out = model.generate(idx, args.new, temperature=0.0, cuda_graph=g)
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                    assert out.shape == (B, args.prompt + args.new)
+                    if rnd > 0:
+                        tps[(w, mode)].append(B * args.new / dt)
+                model.drop_decode_weights()
+        res = {"model": args.model, "batch": B, "prompt": args.prompt, "new_tokens": args.new, "rounds": args.rounds}
+        for (w, mode), v in tps.items():
+            res[f"{w}_{mode}_tok_per_s"] = [round(t, 1) for t in v]
+            res[f"{w}_{mode}_median_tok_per_s"] = round(statistics.median(v), 1)
+        for mode in ("eager", "graph"):
+            res[f"fp8_over_bf16_{mode}"] = round(res[f"fp8_{mode}_median_tok_per_s"] / res[f"bf16_{mode}_median_tok_per_s"], 3)
         print(json.dumps(res), flush=True)
 
 

@@ -311,22 +311,34 @@ std::tuple<Tensor, Tensor> gemm_tn(const Tensor& a, const Tensor& b, const std::
 
 // ---------------------------------------------------------------- skinny GEMM (decode)
 // y[M, N] = act(in[M, K] w[N, K]^T (+ bias)) for M <= 8 token rows; in = x, or (gamma given)
-// norm(x (+ res)) -- then also returns the residual stream s = x + res when res is given
-std::tuple<Tensor, Tensor> gemv(const Tensor& x, const Tensor& w, const std::optional<Tensor>& bias,
-                         const std::optional<Tensor>& res, const std::optional<Tensor>& gamma,
-                         const std::optional<Tensor>& beta, double eps, int64_t rms, int64_t act,
-                         const std::optional<Tensor>& kc, const std::optional<Tensor>& vc,
-                         const std::optional<Tensor>& pos, int64_t q_cols) {
+// norm(x (+ res)) -- then also returns the residual stream s = x + res when res is given.
+// wscale == nullptr: w is bf16 (gemv); else w holds e4m3fn codes (uint8) and wscale one fp32 scale per row (gemv_fp8)
+std::tuple<Tensor, Tensor> gemv_impl(const Tensor& x, const Tensor& w, const Tensor* wscale,
+                                     const std::optional<Tensor>& bias, const std::optional<Tensor>& res,
+                                     const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double eps,
+                                     int64_t rms, int64_t act, const std::optional<Tensor>& kc,
+                                     const std::optional<Tensor>& vc, const std::optional<Tensor>& pos,
+                                     int64_t q_cols) {
   check_bf16(x, "x");
-  check_bf16(w, "w");
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "gemv: x [M,K], w [N,K]");
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(M <= pllm::gemv_max_rows(), "gemv: at most ", pllm::gemv_max_rows(), " rows");
-  TORCH_CHECK(K % 8 == 0 && x.stride(1) == 1 && w.stride(1) == 1 && x.stride(0) % 8 == 0 && w.stride(0) % 8 == 0,
-              "gemv: K % 8 == 0, unit column stride, row strides % 8");
+  TORCH_CHECK(K % 8 == 0 && x.stride(1) == 1 && x.stride(0) % 8 == 0, "gemv: K % 8 == 0, x unit column stride, "
+              "row stride % 8");
+  if (wscale) {  // rows of 8-B aligned code chunks
+    check_gpu(w, "wq");
+    TORCH_CHECK(w.scalar_type() == at::kByte && w.is_contiguous(), "gemv_fp8: wq uint8 [N,K], contiguous");
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(w.data_ptr()) & 7) == 0, "gemv_fp8: wq must be 8-byte aligned");
+    check_gpu(*wscale, "wscale");
+    TORCH_CHECK(wscale->scalar_type() == at::kFloat && wscale->dim() == 1 && wscale->size(0) == N &&
+                    wscale->is_contiguous(), "gemv_fp8: wscale fp32 [N], contiguous");
+  } else {
+    check_bf16(w, "w");
+    TORCH_CHECK(w.stride(1) == 1 && w.stride(0) % 8 == 0, "gemv: w unit column stride, row stride % 8");
+    check_aligned16(w, "w");
+  }
   TORCH_CHECK(act >= 0 && act <= 2, "gemv: act 0 (none), 1 (gelu), 2 (relu)");
   check_aligned16(x, "x");
-  check_aligned16(w, "w");
   if (bias) {
     check_bf16(*bias, "bias");
     TORCH_CHECK(bias->numel() == N && bias->is_contiguous(), "gemv: bias [N]");
@@ -380,8 +392,9 @@ std::tuple<Tensor, Tensor> gemv(const Tensor& x, const Tensor& w, const std::opt
     a.lds = K;
     a.eps = (float)eps;
     a.rms = (int)rms;
-    a.w = (const uint16_t*)w.data_ptr();
+    a.w = w.data_ptr();
     a.ldw = w.stride(0);
+    a.wscale = wscale ? wscale->data_ptr<float>() : nullptr;
     a.bias = bias ? (const uint16_t*)bias->data_ptr() : nullptr;
     a.y = (uint16_t*)y.data_ptr();
     a.ldy = N;
@@ -398,10 +411,42 @@ std::tuple<Tensor, Tensor> gemv(const Tensor& x, const Tensor& w, const std::opt
     a.kv_cols = (int)kv_cols;
     a.kv_smax = kc ? (int)kc->size(1) : 0;
     TORCH_CHECK(!a.kc || a.act == 0, "gemv: KV-cache append takes no activation");
-    pllm::gemv(a, cur_stream());
+    if (wscale) pllm::gemv_fp8(a, cur_stream());
+    else pllm::gemv(a, cur_stream());
   }
   if (!res) s = at::empty({0}, x.options());
   return {y, s};
+}
+
+std::tuple<Tensor, Tensor> gemv(const Tensor& x, const Tensor& w, const std::optional<Tensor>& bias,
+                                const std::optional<Tensor>& res, const std::optional<Tensor>& gamma,
+                                const std::optional<Tensor>& beta, double eps, int64_t rms, int64_t act,
+                                const std::optional<Tensor>& kc, const std::optional<Tensor>& vc,
+                                const std::optional<Tensor>& pos, int64_t q_cols) {
+  return gemv_impl(x, w, nullptr, bias, res, gamma, beta, eps, rms, act, kc, vc, pos, q_cols);
+}
+
+// the same contract with the weight as e4m3fn codes wq [N, K] and per-row scales: w = wq * wscale[:, None]
+std::tuple<Tensor, Tensor> gemv_fp8(const Tensor& x, const Tensor& wq, const Tensor& wscale,
+                                    const std::optional<Tensor>& bias, const std::optional<Tensor>& res,
+                                    const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double eps,
+                                    int64_t rms, int64_t act, const std::optional<Tensor>& kc,
+                                    const std::optional<Tensor>& vc, const std::optional<Tensor>& pos,
+                                    int64_t q_cols) {
+  return gemv_impl(x, wq, &wscale, bias, res, gamma, beta, eps, rms, act, kc, vc, pos, q_cols);
+}
+
+// per-row e4m3fn quantisation of a bf16 weight [N, K] (unit column stride): (codes uint8 [N, K], scale fp32 [N])
+std::tuple<Tensor, Tensor> quantize_rows_fp8(const Tensor& w) {
+  check_bf16(w, "w");
+  TORCH_CHECK(w.dim() == 2 && (w.size(1) <= 1 || w.stride(1) == 1), "quantize_rows_fp8: w [N,K], unit column stride");
+  const int64_t N = w.size(0), K = w.size(1);
+  TORCH_CHECK(N < (1ll << 31) && K < (1ll << 31), "quantize_rows_fp8: N, K < 2^31");
+  Tensor q = at::empty({N, K}, w.options().dtype(at::kByte));
+  Tensor scale = at::empty({N}, w.options().dtype(at::kFloat));
+  pllm::quantize_rows_fp8((const uint16_t*)w.data_ptr(), w.stride(0), (uint8_t*)q.data_ptr(), scale.data_ptr<float>(),
+                          (int)N, (int)K, cur_stream());
+  return {q, scale};
 }
 
 // ---------------------------------------------------------------- activations
@@ -1314,6 +1359,8 @@ TORCH_LIBRARY(pllm, m) {
   m.def("wgrad_set_hy(int on) -> ()", [](int64_t on) { pllm::wgrad_set_hy((int)on); });
   m.def("attn_bwd_set_workspace_mb(float mb) -> ()", [](double mb) { g_attn_ws_bytes = (int64_t)(mb * (1 << 20)); });
   m.def("gemv(Tensor x, Tensor w, Tensor? bias, Tensor? res=None, Tensor? gamma=None, Tensor? beta=None, float eps=1e-5, int rms=0, int act=0, Tensor(a!)? kc=None, Tensor(b!)? vc=None, Tensor? pos=None, int q_cols=0) -> (Tensor, Tensor)");
+  m.def("gemv_fp8(Tensor x, Tensor wq, Tensor wscale, Tensor? bias, Tensor? res=None, Tensor? gamma=None, Tensor? beta=None, float eps=1e-5, int rms=0, int act=0, Tensor(a!)? kc=None, Tensor(b!)? vc=None, Tensor? pos=None, int q_cols=0) -> (Tensor, Tensor)");
+  m.def("quantize_rows_fp8(Tensor w) -> (Tensor, Tensor)");
   m.def("act_fwd(Tensor x, int op) -> Tensor");
   m.def("act_bwd(Tensor dy, Tensor x, int op) -> Tensor");
   m.def("act_bwd_bias(Tensor dy, Tensor x, int op, Tensor(a!) bias_acc) -> Tensor");
@@ -1381,5 +1428,7 @@ TORCH_LIBRARY_IMPL(pllm, CUDA, m) {
   m.impl("attn_decode", attn_decode);
   m.impl("attn_sink_bwd", attn_sink_bwd);
   m.impl("gemv", gemv);
+  m.impl("gemv_fp8", gemv_fp8);
+  m.impl("quantize_rows_fp8", quantize_rows_fp8);
   m.impl("attn_bwd", attn_bwd);
 }

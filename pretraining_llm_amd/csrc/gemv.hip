@@ -16,6 +16,14 @@
 // one workgroup per 1-4 columns, its 64-256 lanes striding the K chunks of those columns
 // together, partial sums reduced across waves through LDS -> 576-768 workgroups.
 // Requires K % 8 == 0 and 16-B aligned rows (host-checked).
+//
+// Weight-only FP8 (gemv_fp8): the same two kernels instantiated with FP8 = true read the weights as OCP
+// e4m3fn codes, one byte each, with one fp32 scale per output column.  The lane <-> K mapping is unchanged (a
+// lane owns 8 consecutive K elements per step: an 8-B non-temporal weight load per column instead of 16 B), the
+// codes are converted exactly by v_cvt_pk_f32_fp8 (4 converts per 8 weights) and multiplied into the same fp32
+// chains, and the scale is applied once per output in the epilogue: v = fma(sum of the waves in order,
+// wscale[n], bias[n]).  Requires K % 8 == 0 and 8-B aligned code rows.  The bf16 instantiations compile to
+// the code they had before the template parameter existed.
 #include "common.h"
 #include "kernels.h"
 
@@ -24,26 +32,62 @@ namespace {
 constexpr int GV_THREADS = 256;
 constexpr int GV_COLS = 4;  // output columns per wave
 
-template <int M>
+// one lane's 8 consecutive weights of a column: 16 B of bf16, or 8 B of e4m3fn codes
+template <bool FP8>
+struct WChunk {
+  typedef u32x4 type;
+};
+template <>
+struct WChunk<true> {
+  typedef u32x2 type;
+};
+template <bool FP8>
+PL_DEV typename WChunk<FP8>::type ldw_nt(const void* w, int64_t elem) {
+  if constexpr (FP8) return __builtin_nontemporal_load(reinterpret_cast<const u32x2*>((const uint8_t*)w + elem));
+  else return ld16_nt((const uint16_t*)w + elem);
+}
+PL_DEV void unpackw(const u32x4& v, float* f) { unpack8(v, f); }
+PL_DEV void unpackw(const u32x2& v, float* f) {  // byte i of the 8 is element i
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], true);
+    f[4 * i] = lo[0];
+    f[4 * i + 1] = lo[1];
+    f[4 * i + 2] = hi[0];
+    f[4 * i + 3] = hi[1];
+  }
+}
+
+template <int M, bool FP8>
 __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const uint16_t* __restrict__ x, int64_t ldx,
-                                                          const uint16_t* __restrict__ w, int64_t ldw,
+                                                          const void* __restrict__ w, int64_t ldw,
+                                                          const float* __restrict__ wscale,
                                                           const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
                                                           int64_t ldy, int N, int K, int Mr) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n0 = (blockIdx.x * (GV_THREADS / 64) + wave) * GV_COLS;
   if (n0 >= N) return;  // wave-uniform
   const int nch = K >> 3;
+  // FP8: the epilogue's scales are requested here, so their latency hides behind the weight stream instead of
+  // following the reduction; the column index is wave-uniform, so they are scalar loads into SGPRs
+  float sc[GV_COLS];
+  if constexpr (FP8) {
+    const int n0u = __builtin_amdgcn_readfirstlane(n0);
+#pragma unroll
+    for (int c = 0; c < GV_COLS; ++c) sc[c] = wscale[min(n0u + c, N - 1)];
+  }
   float acc[GV_COLS][M];
 #pragma unroll
   for (int c = 0; c < GV_COLS; ++c)
 #pragma unroll
     for (int m = 0; m < M; ++m) acc[c][m] = 0.f;
   for (int ch = lane; ch < nch; ch += 64) {
-    u32x4 wr[GV_COLS];
+    typename WChunk<FP8>::type wr[GV_COLS];
 #pragma unroll
     for (int c = 0; c < GV_COLS; ++c) {  // weight chunks first (the streamed bytes)
       const int n = min(n0 + c, N - 1);
-      wr[c] = ld16_nt(w + (int64_t)n * ldw + ch * 8);
+      wr[c] = ldw_nt<FP8>(w, (int64_t)n * ldw + ch * 8);
     }
     float xf[M][8];
 #pragma unroll
@@ -58,7 +102,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const uint16_t* __rest
 #pragma unroll
     for (int c = 0; c < GV_COLS; ++c) {
       float wf[8];
-      unpack8(wr[c], wf);
+      unpackw(wr[c], wf);
 #pragma unroll
       for (int m = 0; m < M; ++m)
 #pragma unroll
@@ -76,8 +120,13 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const uint16_t* __rest
       if (n < N) {
         const float b = bias ? bf2f(bias[n]) : 0.f;
 #pragma unroll
-        for (int m = 0; m < M; ++m)
-          if (m < Mr) y[(int64_t)m * ldy + n] = f2bf_bits(acc[c][m] + b);
+        for (int m = 0; m < M; ++m) {
+          if constexpr (FP8) {
+            if (m < Mr) y[(int64_t)m * ldy + n] = f2bf_bits(fmaf(acc[c][m], sc[c], b));
+          } else {
+            if (m < Mr) y[(int64_t)m * ldy + n] = f2bf_bits(acc[c][m] + b);
+          }
+        }
       }
     }
   }
@@ -113,7 +162,7 @@ PL_DEV void block_sum(float (&v)[M], float* red) {
 // With a.kc set (decode QKV projection) the K and V columns are also appended to the KV cache at
 // the device-side position *a.pos.  Roundings follow the unfused path: x + res, the normalised input and the pre-activation are
 // rounded to bf16 where the separate kernels would have stored them.
-template <int M, int C, int T, bool NORM>
+template <int M, int C, int T, bool NORM, bool FP8>
 __global__ __launch_bounds__(T) void gemv_splitk_kernel(const pllm::GemvArgs a) {
   constexpr int NW = T / 64;
   __shared__ float part[NW][C * M];
@@ -122,14 +171,14 @@ __global__ __launch_bounds__(T) void gemv_splitk_kernel(const pllm::GemvArgs a) 
   const int nch = a.K >> 3, Mr = a.Mr, N = a.N;
   const uint16_t* __restrict__ x = a.x;
   const uint16_t* __restrict__ res = a.res;
-  const uint16_t* __restrict__ w = a.w;
+  const void* __restrict__ w = a.w;
   float mean[M], rstd[M];
   // the first weight chunks are requested before the norm statistics so their HBM latency
   // overlaps the statistics pass and its block reduction
-  u32x4 wpre[C];
+  typename WChunk<FP8>::type wpre[C];
   if (threadIdx.x < nch) {
 #pragma unroll
-    for (int c = 0; c < C; ++c) wpre[c] = ld16_nt(w + (int64_t)min(n0 + c, N - 1) * a.ldw + threadIdx.x * 8);
+    for (int c = 0; c < C; ++c) wpre[c] = ldw_nt<FP8>(w, (int64_t)min(n0 + c, N - 1) * a.ldw + threadIdx.x * 8);
   }
   if constexpr (NORM) {
     // one statistics pass (sums of s and s^2 in fp32; var = E[s^2] - E[s]^2 -- a shift by the
@@ -168,19 +217,28 @@ __global__ __launch_bounds__(T) void gemv_splitk_kernel(const pllm::GemvArgs a) 
       rstd[m] = rsqrtf(fmaxf(st[M + m] * invK - mean[m] * mean[m], 0.f) + a.eps);
     }
   }
+  // FP8: the epilogue's scale and bias of this thread's output are requested ahead of the weight stream
+  float sc_pre = 1.f, b_pre = 0.f;
+  if constexpr (FP8) {
+    if ((int)threadIdx.x < C * M) {
+      const int n = min(n0 + (int)threadIdx.x / M, N - 1);
+      sc_pre = a.wscale[n];
+      b_pre = a.bias ? bf2f(a.bias[n]) : 0.f;
+    }
+  }
   float acc[C][M];
 #pragma unroll
   for (int c = 0; c < C; ++c)
 #pragma unroll
     for (int m = 0; m < M; ++m) acc[c][m] = 0.f;
   for (int ch = threadIdx.x; ch < nch; ch += T) {
-    u32x4 wr[C];
+    typename WChunk<FP8>::type wr[C];
     if (ch == (int)threadIdx.x) {
 #pragma unroll
       for (int c = 0; c < C; ++c) wr[c] = wpre[c];
     } else {
 #pragma unroll
-      for (int c = 0; c < C; ++c) wr[c] = ld16_nt(w + (int64_t)min(n0 + c, N - 1) * a.ldw + ch * 8);
+      for (int c = 0; c < C; ++c) wr[c] = ldw_nt<FP8>(w, (int64_t)min(n0 + c, N - 1) * a.ldw + ch * 8);
     }
     float g[8], bt[8];
     if constexpr (NORM) {
@@ -215,7 +273,7 @@ __global__ __launch_bounds__(T) void gemv_splitk_kernel(const pllm::GemvArgs a) 
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       float wf[8];
-      unpack8(wr[c], wf);
+      unpackw(wr[c], wf);
 #pragma unroll
       for (int m = 0; m < M; ++m)
 #pragma unroll
@@ -234,9 +292,17 @@ __global__ __launch_bounds__(T) void gemv_splitk_kernel(const pllm::GemvArgs a) 
   if (t < C * M) {
     const int c = t / M, m = t % M, n = n0 + c;
     if (n < N && m < Mr) {
-      float v = a.bias ? bf2f(a.bias[n]) : 0.f;
+      float v;
+      if constexpr (FP8) {  // the row scale once per output: the waves in order, then fma(sum, scale, bias)
+        float sum = 0.f;
 #pragma unroll
-      for (int i = 0; i < NW; ++i) v += part[i][t];
+        for (int i = 0; i < NW; ++i) sum += part[i][t];
+        v = fmaf(sum, sc_pre, b_pre);
+      } else {
+        v = a.bias ? bf2f(a.bias[n]) : 0.f;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) v += part[i][t];
+      }
       if (a.act == 1) v = gelu_f(bf16_round(v));
       else if (a.act == 2) v = fmaxf(v, 0.f);
       const uint16_t o = f2bf_bits(v);
@@ -252,12 +318,12 @@ __global__ __launch_bounds__(T) void gemv_splitk_kernel(const pllm::GemvArgs a) 
   }
 }
 
-template <int M, bool NORM>
+template <int M, bool NORM, bool FP8>
 void launch_splitk(const pllm::GemvArgs& a, hipStream_t st) {
   const int nch = a.K >> 3;
   const int C = a.N <= 1024 ? 1 : a.N <= 2048 ? 2 : 4;  // >= 512 workgroups for N >= 512
   const dim3 grid((a.N + C - 1) / C);
-#define LS(CC, TT) hipLaunchKernelGGL((gemv_splitk_kernel<M, CC, TT, NORM>), grid, dim3(TT), 0, st, a)
+#define LS(CC, TT) hipLaunchKernelGGL((gemv_splitk_kernel<M, CC, TT, NORM, FP8>), grid, dim3(TT), 0, st, a)
 #define LC(CC)                     \
   if (nch > 128) LS(CC, 256);      \
   else if (nch > 64) LS(CC, 128);  \
@@ -273,31 +339,28 @@ void launch_splitk(const pllm::GemvArgs& a, hipStream_t st) {
 #undef LS
 }
 
-template <bool NORM>
+template <bool NORM, bool FP8>
 void dispatch_splitk(const pllm::GemvArgs& a, hipStream_t st) {
-  if (a.Mr <= 1) launch_splitk<1, NORM>(a, st);
-  else if (a.Mr <= 2) launch_splitk<2, NORM>(a, st);
-  else if (a.Mr <= 4) launch_splitk<4, NORM>(a, st);
-  else launch_splitk<8, NORM>(a, st);
+  if (a.Mr <= 1) launch_splitk<1, NORM, FP8>(a, st);
+  else if (a.Mr <= 2) launch_splitk<2, NORM, FP8>(a, st);
+  else if (a.Mr <= 4) launch_splitk<4, NORM, FP8>(a, st);
+  else launch_splitk<8, NORM, FP8>(a, st);
 }
 
-}  // namespace
-
-namespace pllm {
-
-int gemv_max_rows() { return 8; }
-
-void gemv(const GemvArgs& a, hipStream_t st) {
+// the dispatch of both weight formats: the split-K form for N < 8192 and for any call with a prologue, an
+// activation or a KV append, else the wide form
+template <bool FP8>
+void gemv_any(const pllm::GemvArgs& a, hipStream_t st) {
   if (a.gamma) {
-    dispatch_splitk<true>(a, st);
+    dispatch_splitk<true, FP8>(a, st);
   } else if (a.N < 8192 || a.act != 0 || a.kc) {
-    dispatch_splitk<false>(a, st);
+    dispatch_splitk<false, FP8>(a, st);
   } else {
     const int cols_per_block = GV_COLS * (GV_THREADS / 64);
     const dim3 grid((a.N + cols_per_block - 1) / cols_per_block);
 #define L(MM)                                                                                                  \
-  hipLaunchKernelGGL((gemv_kernel<MM>), grid, dim3(GV_THREADS), 0, st, a.x, a.ldx, a.w, a.ldw, a.bias, a.y,     \
-                     a.ldy, a.N, a.K, a.Mr)
+  hipLaunchKernelGGL((gemv_kernel<MM, FP8>), grid, dim3(GV_THREADS), 0, st, a.x, a.ldx, a.w, a.ldw, a.wscale,  \
+                     a.bias, a.y, a.ldy, a.N, a.K, a.Mr)
     if (a.Mr <= 1) L(1);
     else if (a.Mr <= 2) L(2);
     else if (a.Mr <= 4) L(4);
@@ -306,5 +369,15 @@ void gemv(const GemvArgs& a, hipStream_t st) {
   }
   PL_CHECK_LAUNCH();
 }
+
+}  // namespace
+
+namespace pllm {
+
+int gemv_max_rows() { return 8; }
+
+void gemv(const GemvArgs& a, hipStream_t st) { gemv_any<false>(a, st); }
+
+void gemv_fp8(const GemvArgs& a, hipStream_t st) { gemv_any<true>(a, st); }
 
 }  // namespace pllm

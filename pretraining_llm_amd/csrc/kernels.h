@@ -194,7 +194,9 @@ void sample_rows(const void* logits, bool bf16_in, int64_t ld, int B, int V, con
                  int64_t* tokens, int* kept, float* min_kept, hipStream_t st);
 
 // gemv.hip: y[M, N] = act(in[M, K] W[N, K]^T + bias) for M <= gemv_max_rows() (decode projections),
-// in = x, or norm(x + res) with the residual stream x + res written to s_out when gamma is set
+// in = x, or norm(x + res) with the residual stream x + res written to s_out when gamma is set.
+// gemv_fp8: W is given as OCP e4m3fn codes (one byte each, ldw in bytes) with one fp32 scale per row:
+// y = act((in . codes^T) * wscale + bias)
 struct GemvArgs {
   const uint16_t* x;
   int64_t ldx;
@@ -206,7 +208,7 @@ struct GemvArgs {
   int64_t lds;
   float eps;
   int rms;
-  const uint16_t* w;
+  const void* w;          // bf16 (gemv) or e4m3fn codes (gemv_fp8); ldw in elements
   int64_t ldw;
   const uint16_t* bias;   // nullable
   uint16_t* y;
@@ -221,9 +223,15 @@ struct GemvArgs {
   int pos_per_row;  // pos holds one position per row (continuous batching) instead of one
   int64_t kv_ldb;
   int q_cols, kv_cols, kv_smax;  // positions outside [0, kv_smax) are dropped, never written
+  const float* wscale;  // nullable: gemv_fp8 only, one scale per row of w [N] (last: the bf16 kernels' argument layout stays)
 };
 int gemv_max_rows();
 void gemv(const GemvArgs& a, hipStream_t st);
+void gemv_fp8(const GemvArgs& a, hipStream_t st);
+
+// quant_fp8.hip: per-row weight quantiser of the FP8 decode path.  scale[n] = max_k |w[n, k]| / 448 (1 for an
+// all-zero row), q[n, k] = the e4m3fn code nearest to w[n, k] / scale[n] (ties to even)
+void quantize_rows_fp8(const uint16_t* w, int64_t ldw, uint8_t* q, float* scale, int N, int K, hipStream_t st);
 
 // attention.hip
 bool attn_supported_head_dim(int D);

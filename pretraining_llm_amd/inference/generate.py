@@ -20,6 +20,7 @@ from typing import Optional
 import torch
 
 from .. import ops
+from ..models.gpt import decode_weight
 
 
 class KVCache:
@@ -60,7 +61,7 @@ def forward_cached(model, idx: torch.Tensor, cache: KVCache, pos: int,
         rl = res[rows, last].unsqueeze(1) if res is not None else None
     else:
         xl, rl = x[:, -1:], (res[:, -1:] if res is not None else None)
-    logits, _ = model.layer_norm.linear(xl, rl, model.head_weight, model.head_bias)
+    logits, _ = model.layer_norm.linear(xl, rl, decode_weight(model.head_weight), model.head_bias)
     return ops.softcap(logits[:, -1, :].float(), cfg.final_logit_softcap)
 
 
@@ -78,7 +79,7 @@ def forward_decode(model, tok: torch.Tensor, cache: KVCache, pos_t: torch.Tensor
     res = None
     for i, blk in enumerate(model.attn_blocks):
         x, res = blk.forward_decode(x, res, cache, i, pos_t, len_t, rope)
-    logits, _ = model.layer_norm.linear(x, res, model.head_weight, model.head_bias)
+    logits, _ = model.layer_norm.linear(x, res, decode_weight(model.head_weight), model.head_bias)
     # (final-logit soft-capping: elementwise torch ops on [B, V], captured with the rest of the step)
     return ops.softcap(logits[:, -1, :].float(), cfg.final_logit_softcap)
 

@@ -38,6 +38,13 @@ def hbm_free_bytes(device) -> int:
     return int(free + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device))
 
 
+def decode_weight(p):
+    """What the cached / decode paths hand to ``ops.linear`` / ``Norm.linear`` for parameter ``p``: its quantised
+    decode copy (``GPT.quantize_decode_weights``) when it has one, else ``p`` itself."""
+    fw = getattr(p, "_pllm_decode_weight", None)
+    return p if fw is None else fw
+
+
 class Norm(nn.Module):
     def __init__(self, cfg: ModelConfig):
         super().__init__()
@@ -126,7 +133,7 @@ class Attention(nn.Module):
     # --- KV-cache decode -------------------------------------------------
     def forward_cached(self, x, cache, layer_idx, pos, rope=None, qkv=None):
         if qkv is None:
-            qkv = ops.linear(x, self.qkv.weight, self.qkv.bias)
+            qkv = ops.linear(x, decode_weight(self.qkv.weight), self.qkv.bias)
         B, T, _ = qkv.shape
         H, Hkv, D = self.n_head, self.n_kv_head, self.head_dim
         q = qkv[..., : H * D].view(B, T, H, D)
@@ -155,7 +162,7 @@ class Attention(nn.Module):
             y = ops.attention(q.contiguous(), kc, vc, causal=True, **self._sinks_kw())
         y = y.reshape(B, T, H * D)
         if self.proj is not None:
-            y = ops.linear(y, self.proj.weight, self.proj.bias)
+            y = ops.linear(y, decode_weight(self.proj.weight), self.proj.bias)
         return y
 
     def forward_decode(self, x, cache, layer_idx, pos_t, len_t, rope=None, qkv=None, kv_written=False):
@@ -165,7 +172,7 @@ class Attention(nn.Module):
         ``qkv``: the already-projected input (the block fuses ln1 into the projection);
         ``kv_written``: that projection already appended k/v to the cache (no RoPE only)."""
         if qkv is None:
-            qkv = ops.linear(x, self.qkv.weight, self.qkv.bias)
+            qkv = ops.linear(x, decode_weight(self.qkv.weight), self.qkv.bias)
         B = qkv.shape[0]
         H, Hkv, D = self.n_head, self.n_kv_head, self.head_dim
         q = qkv[..., : H * D].view(B, 1, H, D)
@@ -200,7 +207,7 @@ class Attention(nn.Module):
                                  window=self.window, **self._sinks_kw())
         y = y.reshape(B, 1, H * D)
         if self.proj is not None:
-            y = ops.linear(y, self.proj.weight, self.proj.bias)
+            y = ops.linear(y, decode_weight(self.proj.weight), self.proj.bias)
         return y
 
 
@@ -305,13 +312,13 @@ class Block(nn.Module):
     def _mlp_infer(self, a, res):
         kind = self.mlp.kind
         act = None if kind == "swiglu" else ("gelu" if kind == "gelu" else "relu")
-        h, res2 = self.ln2.linear(a, res, self.mlp.hidden.weight, self.mlp.hidden.bias, act=act)
+        h, res2 = self.ln2.linear(a, res, decode_weight(self.mlp.hidden.weight), self.mlp.hidden.bias, act=act)
         if kind == "swiglu":
             h = ops.swiglu(h)
-        return ops.linear(h, self.mlp.proj.weight, self.mlp.proj.bias), res2
+        return ops.linear(h, decode_weight(self.mlp.proj.weight), self.mlp.proj.bias), res2
 
     def forward_cached(self, x, residual, cache, layer_idx, pos, rope=None):
-        qkv, res = self.ln1.linear(x, residual, self.attn.qkv.weight, self.attn.qkv.bias)
+        qkv, res = self.ln1.linear(x, residual, decode_weight(self.attn.qkv.weight), self.attn.qkv.bias)
         a = self.attn.forward_cached(None, cache, layer_idx, pos, rope, qkv=qkv)
         return self._mlp_infer(a, res)
 
@@ -321,7 +328,7 @@ class Block(nn.Module):
         kv = None
         if rope is None and not getattr(self.attn, "qk_norm", False):
             kv = (cache.k[layer_idx], cache.v[layer_idx], pos_t, self.attn.n_head * self.attn.head_dim)
-        qkv, res = self.ln1.linear(x, residual, self.attn.qkv.weight, self.attn.qkv.bias, kv=kv)
+        qkv, res = self.ln1.linear(x, residual, decode_weight(self.attn.qkv.weight), self.attn.qkv.bias, kv=kv)
         a = self.attn.forward_decode(None, cache, layer_idx, pos_t, len_t, rope, qkv=qkv,
                                      kv_written=kv is not None)
         return self._mlp_infer(a, res)
@@ -363,6 +370,7 @@ class GPT(nn.Module):
         # on the loss's device; written with copy_ so that a replayed hipGraph refreshes it.  Not a registered buffer
         self.z_term = None
         self.parallel = None  # ParallelGroups once parallel.model_parallel.parallelize_gpt ran
+        self._decode_weights = None  # "fp8" once quantize_decode_weights ran
         self.reset_parameters()
 
     # ------------------------------------------------------------------
@@ -393,6 +401,69 @@ class GPT(nn.Module):
     @property
     def head_bias(self):
         return None if self.lm_head is None else self.lm_head.bias
+
+    # ------------------------------------------------------------------ weight-only FP8 decode
+    def _decode_weight_params(self):
+        """(name, parameter) of every weight the cached / decode paths multiply by: the four projections of each
+        block and the head (with tied embeddings the token table; the embedding lookup itself stays bf16)."""
+        out = []
+        for i, blk in enumerate(self.attn_blocks):
+            lins = (("attn.qkv", blk.attn.qkv), ("attn.proj", blk.attn.proj), ("mlp.hidden", blk.mlp.hidden),
+                    ("mlp.proj", blk.mlp.proj))
+            out += [(f"attn_blocks.{i}.{n}.weight", m.weight) for n, m in lins if m is not None]
+        out.append(("token_embed.weight" if self.lm_head is None else "lm_head.weight", self.head_weight))
+        return out
+
+    @property
+    def decode_weights(self) -> Optional[str]:
+        """None (the decode paths read the bf16 parameters) or "fp8" (``quantize_decode_weights``)."""
+        return self._decode_weights
+
+    def quantize_decode_weights(self, fmt: str = "fp8"):
+        """Quantise, per output row to FP8 (OCP e4m3fn, ``ops.quantize_weight_fp8``), every weight that the cached /
+        decode paths multiply by.  Calls of at most 8 token rows then stream 1 byte per weight through the FP8 arms
+        of the skinny GEMM (csrc/gemv.hip); every other call -- prefill, more than 8 rows, training -- keeps reading
+        the bf16 parameters, which stay (+1 byte per quantised parameter).  The quantised copies are a cache of the
+        parameters as they are NOW: ``train()`` and ``load_state_dict`` drop them, ``state_dict()`` has no keys for
+        them, and whoever writes the parameters in another way calls this again.  A weight the kernel cannot take (K
+        not a multiple of 8) stays bf16.  Returns the names of the quantised weights."""
+        if fmt != "fp8":
+            raise ValueError(f"quantize_decode_weights: fmt={fmt!r}, expected 'fp8'")
+        if self.parallel is not None and self.parallel.model_parallel:
+            raise ValueError("quantize_decode_weights needs a dense model: the tensor- / context-parallel attention and "
+                             f"MLP classes take no quantised weights (tp_size={self.parallel.tp}, "
+                             f"cp_size={self.parallel.cp})")
+        if self.training:
+            raise RuntimeError("quantize_decode_weights: call model.eval() first (train() drops the quantised weights)")
+        self.drop_decode_weights()
+        done = []
+        for name, p in self._decode_weight_params():
+            fw = ops.quantize_weight_fp8(p)
+            if fw is not None:
+                p._pllm_decode_weight = fw
+                done.append(name)
+        self._decode_weights = "fp8" if done else None
+        return done
+
+    def drop_decode_weights(self):
+        """Back to the bf16 parameters on every path."""
+        for _, p in self._decode_weight_params():
+            if hasattr(p, "_pllm_decode_weight"):
+                del p._pllm_decode_weight
+        self._decode_weights = None
+
+    def train(self, mode: bool = True):
+        if mode:
+            self.drop_decode_weights()
+        return super().train(mode)
+
+    def load_state_dict(self, *args, **kwargs):
+        self.drop_decode_weights()
+        return super().load_state_dict(*args, **kwargs)
+
+    def _apply(self, fn, *args, **kwargs):  # .to() / .cuda() / .bfloat16(): the codes would describe other tensors
+        self.drop_decode_weights()
+        return super()._apply(fn, *args, **kwargs)
 
     def rope_tables(self, device, length: Optional[int] = None):
         cfg = self.config

@@ -294,8 +294,71 @@ def _weight_grad(dy2, x2, tgt, btgt=None, overwrite: bool = False):
     return dy2.t() @ x2
 
 
+# ---------------------------------------------------------------------------
+# Weight-only FP8 (OCP e4m3fn) decode weights: a per-row quantised CACHE of a bf16 weight that only the
+# skinny GEMM reads (csrc/gemv.hip FP8 arms, <= 8 token rows, no grad).  Everything else -- prefill,
+# training, more than 8 rows -- keeps reading ``ref``, the bf16 parameter it was made from.
+# ---------------------------------------------------------------------------
+FP8_MAX = 448.0     # largest finite e4m3fn value
+FP8_K_CHUNK = 8     # codes a lane of the FP8 skinny GEMM loads per step: K must be a multiple
+
+
+class Fp8Weight:
+    """``ref`` [N, K] (the bf16 parameter), ``q`` uint8 [N, K] e4m3fn codes, ``scale`` fp32 [N]:
+    ref ~= dequantize_fp8(q, scale).  Accepted as ``weight`` by ``linear`` / ``norm_linear``."""
+    __slots__ = ("ref", "q", "scale", "shape")
+
+    def __init__(self, ref, q, scale):
+        self.ref, self.q, self.scale, self.shape = ref, q, scale, ref.shape
+
+
+def quantize_weight_fp8(w) -> Optional[Fp8Weight]:
+    """Per-row e4m3fn quantisation of a weight [N, K] (csrc/quant_fp8.hip for bf16 on the GPU, ``ops.reference`` on
+    the CPU); None when the FP8 skinny GEMM cannot take it (K not a multiple of 8, not contiguous, a GPU weight
+    that is not on the HIP path).  Non-finite weights raise ValueError."""
+    if w.dim() != 2 or w.shape[1] == 0 or w.shape[1] % FP8_K_CHUNK or not w.is_contiguous():
+        return None
+    if w.is_cuda and not (_lib.use_hip(w) and _lib.available()):
+        return None
+    wd = w.detach()
+    if not bool(torch.isfinite(wd).all()):
+        raise ValueError("quantize_weight_fp8: the weight holds non-finite values")
+    q, scale = _ops().quantize_rows_fp8(wd) if w.is_cuda else ref.quantize_rows_fp8(wd)
+    return Fp8Weight(w, q, scale)
+
+
+def dequantize_fp8(q, scale):
+    """fp32 [N, K] = e4m3fn value of each code times its row's scale."""
+    return ref.dequantize_fp8(q, scale)
+
+
+def _fp8_rows_ok(x) -> bool:
+    """An inference call of at most 8 token rows: the only calls that read the quantised weight."""
+    K = x.shape[-1]
+    return not torch.is_grad_enabled() and K > 0 and 0 < x.numel() // K <= 8
+
+
+def _linear_fp8(x, fw: Fp8Weight, bias):
+    """x W^T + b from the quantised weight, or None when this call keeps the bf16 weight (more than 8 rows, grad
+    mode).  HIP: the FP8 skinny GEMM; CPU / torch backend: ``ops.reference`` on the dequantised weight."""
+    if not _fp8_rows_ok(x):
+        return None
+    if _gemv_shape_ok(x, fw.q) and x.dtype == fw.ref.dtype:
+        y = _ops().gemv_fp8(x.reshape(-1, x.shape[-1]).contiguous(), fw.q, fw.scale, bias)[0]
+        return y.view(*x.shape[:-1], fw.shape[0])
+    if _hip(x):
+        return None
+    return ref.linear_fp8(x, fw.q, fw.scale, bias)
+
+
 def linear(x, weight, bias=None, bias_grad_external: bool = False, residual=None):
-    """``residual`` (only when resid_gemm_ok holds -- the caller checks): x W^T + b + residual."""
+    """``residual`` (only when resid_gemm_ok holds -- the caller checks): x W^T + b + residual.
+    ``weight`` may be an ``Fp8Weight``: decode-sized inference calls read its codes, every other its ``ref``."""
+    if isinstance(weight, Fp8Weight):
+        y = _linear_fp8(x, weight, bias) if residual is None else None
+        if y is not None:
+            return y
+        weight = weight.ref
     if _hip_op("linear", x) and torch.is_grad_enabled() and weight.requires_grad:
         return _LinearFn.apply(x, weight, bias, _bias_ext(bias_grad_external, bias), residual)
     if residual is not None:
@@ -544,8 +607,15 @@ def norm_linear(x, residual, norm_weight, norm_bias, eps: float, rms: bool, weig
 
     ``kv = (k_cache, v_cache, pos_t, q_cols)`` (decode QKV projection, caches [B, S_max, Hkv, D],
     ``pos_t`` int64 [1] on the device): output columns q_cols.. are also appended to the caches
-    at position ``pos_t`` -- by the kernel's epilogue on the fused path."""
-    if _gemv_ok(x, weight) and norm_weight.dtype == x.dtype:
+    at position ``pos_t`` -- by the kernel's epilogue on the fused path.
+
+    ``weight`` may be an ``Fp8Weight``: the fused launch is then ``gemv_fp8`` on its codes; where the fused path
+    does not apply, the unfused sequence hands it to ``linear``, which reads the codes or ``ref`` by its own rule."""
+    fw = weight if isinstance(weight, Fp8Weight) else None
+    if fw is not None:  # the fused launch reads the codes; whatever else runs below decides in linear()
+        weight = fw.ref
+    fused_fp8 = fw is not None and _gemv_ok(x, fw.q) and norm_weight.dtype == x.dtype == weight.dtype
+    if fused_fp8 or (_gemv_ok(x, weight) and norm_weight.dtype == x.dtype):
         K = x.shape[-1]
         rows = x.numel() // K
         x2 = x.reshape(rows, K).contiguous()
@@ -554,8 +624,8 @@ def norm_linear(x, residual, norm_weight, norm_bias, eps: float, rms: bool, weig
         q_cols = 0
         if kv is not None:
             kc, vc, pos, q_cols = kv
-        out = _ops().gemv(x2, weight, bias, r2, norm_weight, None if rms else norm_bias, eps, int(rms),
-                          _ACT_IDS[act], kc, vc, pos, q_cols)
+        tail = (bias, r2, norm_weight, None if rms else norm_bias, eps, int(rms), _ACT_IDS[act], kc, vc, pos, q_cols)
+        out = _ops().gemv_fp8(x2, fw.q, fw.scale, *tail) if fused_fp8 else _ops().gemv(x2, weight, *tail)
         y = out[0].view(*x.shape[:-1], weight.shape[0])
         s = out[1].view(x.shape) if residual is not None else x
         return y, s
@@ -563,7 +633,7 @@ def norm_linear(x, residual, norm_weight, norm_bias, eps: float, rms: bool, weig
         h, s = rms_norm(x, norm_weight, eps, residual)
     else:
         h, s = layer_norm(x, norm_weight, norm_bias, eps, residual)
-    y = linear(h, weight, bias)
+    y = linear(h, fw if fw is not None else weight, bias)
     if act == "gelu":
         y = gelu(y)
     elif act == "relu":

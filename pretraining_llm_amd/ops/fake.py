@@ -200,3 +200,13 @@ def register() -> None:
           q_cols=0):
         y = x.new_empty((x.shape[0], w.shape[0]))
         return (y, x.new_empty(x.shape if res is not None else (0,)))
+
+    @_reg("gemv_fp8")
+    def _(x, wq, wscale, bias, res=None, gamma=None, beta=None, eps=1e-5, rms=0, act=0, kc=None, vc=None, pos=None,
+          q_cols=0):
+        y = x.new_empty((x.shape[0], wq.shape[0]))
+        return (y, x.new_empty(x.shape if res is not None else (0,)))
+
+    @_reg("quantize_rows_fp8")
+    def _(w):
+        return (w.new_empty(w.shape, dtype=torch.uint8), w.new_empty((w.shape[0],), dtype=f32))

@@ -124,6 +124,29 @@ def attention_bwd(do, q, k, v, o, lse, causal: bool = True, scale: Optional[floa
     return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2)
 
 
+def quantize_rows_fp8(w):
+    """Per-row e4m3fn quantisation (csrc/quant_fp8.hip): scale = amax / 448 (1 for an all-zero row), codes =
+    nearest e4m3fn value of w / scale (true divisions, ties to even) -> (uint8 [N, K], fp32 [N])."""
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=1)
+    scale = torch.where(amax == 0, torch.ones_like(amax), amax / 448.0)
+    q = (wf / scale[:, None]).to(torch.float8_e4m3fn)
+    return q.view(torch.uint8), scale
+
+
+def dequantize_fp8(q, scale):
+    """fp32 [N, K]: the e4m3fn value of each code times its row's scale."""
+    return q.view(torch.float8_e4m3fn).to(torch.float32) * scale[:, None].to(torch.float32)
+
+
+def linear_fp8(x, q, scale, bias=None):
+    """x dequantize(q, scale)^T + bias in fp32, rounded once to x.dtype."""
+    y = x.float() @ dequantize_fp8(q, scale).t()
+    if bias is not None:
+        y = y + bias.float()
+    return y.to(x.dtype)
+
+
 def gelu_tanh(x):
     return F.gelu(x.float(), approximate="tanh").to(x.dtype)
 

@@ -30,7 +30,9 @@ def _dtype(device: str, dtype: str):
     return {"bfloat16": torch.bfloat16, "float32": torch.float32}[dtype]
 
 
-def load_model(model_path: str, device: str, dtype: str = "auto"):
+def load_model(model_path: str, device: str, dtype: str = "auto", decode_weights: str = "bf16"):
+    """``decode_weights="fp8"``: decode steps of at most 8 sequences read per-row FP8 copies of the projection and
+    head weights (GPT.quantize_decode_weights); prefill and larger batches keep the bf16 weights."""
     from pretraining_llm_amd.models import GPT, ModelConfig
     from pretraining_llm_amd.models.config import _ref
     from pretraining_llm_amd.utils.checkpoint import load_checkpoint
@@ -42,17 +44,21 @@ def load_model(model_path: str, device: str, dtype: str = "auto"):
                    vocab_size=config['vocab_size'], n_blocks=config['n_blocks'])
     model = GPT(cfg)
     model.load_state_dict(ckpt['model_state_dict'])
-    return model.eval().to(device=device, dtype=_dtype(device, dtype))
+    model = model.eval().to(device=device, dtype=_dtype(device, dtype))
+    if decode_weights != "bf16":
+        model.quantize_decode_weights(decode_weights)
+    return model
 
 
 def generate_tokens(model_path: str, start_ids, max_new_tokens: int = 100, device: str = 'cuda', dtype: str = "auto",
-                    temperature: float = 1.0, top_k=None, seed=None, cuda_graph: bool = True, top_p=None, min_p=None):
+                    temperature: float = 1.0, top_k=None, seed=None, cuda_graph: bool = True, top_p=None, min_p=None,
+                    decode_weights: str = "bf16"):
     """Token-level generation (prompt ids -> prompt + new ids).  With ``top_p`` / ``min_p`` a ``seed`` keys
     the per-row sampler directly (the tokens a server request with that seed gets); without them it
     seeds a torch.Generator as before."""
     if device.startswith("cuda") and not torch.cuda.is_available():
         device = "cpu"
-    model = load_model(model_path, device, dtype)
+    model = load_model(model_path, device, dtype, decode_weights)
     context = torch.tensor(list(start_ids), dtype=torch.long, device=device).unsqueeze(0)
     gen = None
     if seed is not None:
@@ -67,7 +73,7 @@ def generate_tokens(model_path: str, start_ids, max_new_tokens: int = 100, devic
 
 def generate_text(model_path: str, input_text: str, max_new_tokens: int = 100, device: str = 'cuda',
                   temperature: float = 1.0, top_k=None, seed=None, cuda_graph: bool = True, dtype: str = "auto",
-                  top_p=None, min_p=None) -> str:
+                  top_p=None, min_p=None, decode_weights: str = "bf16") -> str:
     from pretraining_llm_amd.data.tokenizer import get_tokenizer
     from pretraining_llm_amd.utils.checkpoint import load_checkpoint
     enc = get_tokenizer(config.get('tokenizer_name', 'gpt2'))
@@ -76,7 +82,7 @@ def generate_text(model_path: str, input_text: str, max_new_tokens: int = 100, d
         vocab = load_checkpoint(model_path).get("model_config", {}).get("vocab_size", config['vocab_size'])
         start_ids = [enc.eot_token % vocab]
     tokens = generate_tokens(model_path, start_ids, max_new_tokens, device, dtype, temperature, top_k, seed, cuda_graph,
-                             top_p, min_p)
+                             top_p, min_p, decode_weights)
     return enc.decode(tokens)
 
 
@@ -94,10 +100,12 @@ def main() -> None:
     parser.add_argument('--dtype', type=str, default='auto', choices=['auto', 'bfloat16', 'float32'],
                         help="auto: bf16 HIP kernels on a GPU, fp32 on the CPU; float32: the reference's precision")
     parser.add_argument('--no_cuda_graph', action='store_true', help='eager decode steps instead of one hipGraph replay')
+    parser.add_argument('--decode_weights', type=str, default='bf16', choices=['bf16', 'fp8'],
+                        help='fp8: decode steps stream per-row FP8 (e4m3) copies of the projection and head weights')
     args = parser.parse_args()
     generated = generate_text(args.model_path, args.input_text, args.max_new_tokens, args.device,
                               args.temperature, args.top_k, args.seed, cuda_graph=not args.no_cuda_graph, dtype=args.dtype,
-                              top_p=args.top_p, min_p=args.min_p)
+                              top_p=args.top_p, min_p=args.min_p, decode_weights=args.decode_weights)
     print(f"Generated text:\n{generated}")
 
 

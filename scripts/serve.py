@@ -32,6 +32,9 @@ def main() -> None:
                          "lockstep: batch only requests with the same prompt length and sampler")
     ap.add_argument("--max_len", type=int, default=None, help="continuous mode: KV-cache length per slot "
                     "(default: the model's context length)")
+    ap.add_argument("--decode_weights", default="bf16", choices=["bf16", "fp8"],
+                    help="fp8: decode steps of at most 8 sequences stream per-row FP8 (e4m3) copies of the projection "
+                         "and head weights; larger batches keep reading the bf16 weights")
     args = ap.parse_args()
     import uvicorn
 
@@ -40,7 +43,7 @@ def main() -> None:
     from pretraining_llm_amd.inference.server import ContinuousGenerationServer, GenerationServer, create_app
     from scripts.generate_text import load_model
     device = args.device if (not args.device.startswith("cuda") or torch.cuda.is_available()) else "cpu"
-    model = load_model(args.model_path, device)
+    model = load_model(args.model_path, device, decode_weights=args.decode_weights)
     if args.mode == "continuous":
         server = ContinuousGenerationServer(model, max_batch=args.max_batch, max_len=args.max_len,
                                             cuda_graph=not args.no_cuda_graph)
