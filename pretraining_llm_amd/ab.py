@@ -16,6 +16,7 @@ choice on the same box without a rebuild.  The C++ side reads the same variable 
 | wgrad_bias | 1 | 0: bias gradients as a separate column-sum pass | r3s3_wgrad_fused_bias_ab.txt |
 | wgrad_variant | -- | torch.ops.pllm.wgrad_set_mfma value: 0 the default dispatch, 100 the one-barrier kernel of csrc/gemm_wgrad.hip (MFMA shape per problem), 16 / 32 that kernel with the MFMA shape forced; any other value acts as 100 | r3_wgrad_asym_ab.md, r2_wgrad_4wave_negative.jsonl and the other r2_wgrad_* records |
 | wgrad_hy_cost | 1 | 0: the hybrid weight gradient's remainder as one round of slices (ctas / rem) instead of the cost model's count | r6_wgrad_hy_cost.log |
+| wgrad_defer | 1 | 0: every weight gradient launched in its layer's backward instead of queued for grouped whole-tile launches (one rank only) | wgrad_grouped.md |
 | wgrad_hy | -- | 0 / 1: hybrid whole-tile + sliced-last-round weight-gradient split | r4_wgrad_hybrid.md |
 | gemm_persistent | -- | 0 / 1: persistent GEMM grids (default: automatic, train/graph.py) | r4_gemm_persistent_ab.txt |
 | dp_world1 | 0 | 1: the DP engine's gradient hooks + bucketed all-reduces at world 1 (a one-rank RCCL rehearsal of the world > 1 step) | tests/test_dp_gpu.py |
@@ -29,7 +30,7 @@ When a key is read -- setting PLLM_AB later than that does nothing for it:
 
 * at import of ``pretraining_llm_amd.ops``, frozen into a module constant: resid_gemm (``RESID_GEMM``), attn_proj_fused
   (``FUSED_ATTN_PROJ``), fused_swiglu_fwd (``FUSED_SWIGLU_FWD``), lt_relu (``LT_RELU_FWD``), wgrad_bias
-  (``FUSED_WGRAD_BIAS``), ce_chunk_rows (``CE_CHUNK_ROWS``).  The ops read the constant on every call, so a test
+  (``FUSED_WGRAD_BIAS``), wgrad_defer (``WGRAD_DEFER``), ce_chunk_rows (``CE_CHUNK_ROWS``).  The ops read the constant on every call, so a test
   flips one with ``monkeypatch.setattr(ops, "FUSED_WGRAD_BIAS", False)``, not through the environment;
 * once per process: wgrad_variant, wgrad_hy and gemm_persistent when the extension is loaded (ops/_lib.py); ce_nt at
   the first cross-entropy launch (a C++ static);

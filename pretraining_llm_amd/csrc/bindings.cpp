@@ -209,6 +209,59 @@ Tensor wgrad(const Tensor& dy, const Tensor& x, const std::optional<Tensor>& out
   return out_acc ? at::empty({0}, dy.options()) : out;
 }
 
+// Whole tiles [first, last) of the global tile list of the problems (dys[i], xs[i]) -> outs[i] (fp32 [P, Q],
+// stored when overwrite[i] else added to), in one launch of the ping-pong kernel's grouped arm; biases[i]
+// (fp32 [P], or an empty tensor for none) gets the column sums of dys[i]'s row bands in the range added.
+// A problem's tiles count row band by row band, 256 x 256 each; the caller cuts the ranges (wgrad_group_plan).
+void wgrad_group(at::TensorList dys, at::TensorList xs, at::TensorList outs, at::TensorList biases,
+                 at::IntArrayRef overwrite, int64_t first, int64_t last) {
+  const size_t n = dys.size();
+  TORCH_CHECK(n >= 1 && n <= (size_t)pllm::kWgradGroupMax, "wgrad_group: 1..", pllm::kWgradGroupMax, " problems");
+  TORCH_CHECK(xs.size() == n && outs.size() == n && biases.size() == n && overwrite.size() == n,
+              "wgrad_group: one x, out, bias and overwrite flag per dy");
+  pllm::WgradGroup g{};
+  g.np = (int)n;
+  for (size_t i = 0; i < n; ++i) {
+    const Tensor &dy = dys[i], &x = xs[i], &out = outs[i], &b = biases[i];
+    check_bf16(dy, "dy");
+    check_bf16(x, "x");
+    TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && dy.size(0) == x.size(0), "wgrad_group: dy [M,P], x [M,Q]");
+    TORCH_CHECK(dy.stride(1) == 1 && x.stride(1) == 1, "wgrad_group: unit column stride");
+    const int64_t M = dy.size(0), P = dy.size(1), Q = x.size(1);
+    TORCH_CHECK(P % 8 == 0 && Q % 8 == 0 && dy.stride(0) % 8 == 0 && x.stride(0) % 8 == 0, "wgrad_group: dims % 8");
+    TORCH_CHECK(P > 0 && Q > 0 && P < (1 << 24) && Q < (1 << 24) && dy.stride(0) < (1 << 24) && x.stride(0) < (1 << 24),
+                "wgrad_group: dims and row strides in [1, 2^24)");
+    TORCH_CHECK(M % 64 == 0 && M >= 128 && M < (1ll << 31), "wgrad_group: M (tokens) a multiple of 64, >= 128");
+    check_aligned16(dy, "dy");
+    check_aligned16(x, "x");
+    TORCH_CHECK(check_grad(out, P * Q, "wgrad_group: out"), "wgrad_group: fp32 gradient targets");
+    check_aligned16(out, "out");
+    if (b.numel() > 0) TORCH_CHECK(check_grad(b, P, "wgrad_group: bias"), "wgrad_group: fp32 bias targets");
+    pllm::WgradGroupProblem& p = g.p[i];
+    p.A = dy.data_ptr();
+    p.B = x.data_ptr();
+    p.lda = dy.stride(0);
+    p.ldb = x.stride(0);
+    p.out = out.data_ptr<float>();
+    p.bias_out = b.numel() > 0 ? b.data_ptr<float>() : nullptr;
+    p.M = (int)M;
+    p.P = (int)P;
+    p.Q = (int)Q;
+    p.accumulate = overwrite[i] ? 0 : 1;
+    const int64_t nt = (int64_t)pllm::plan_tiles((int)P, pllm::kPlanTile) * pllm::plan_tiles((int)Q, pllm::kPlanTile);
+    TORCH_CHECK(g.pre[i] + nt < (1 << 30), "wgrad_group: tile count");
+    g.pre[i + 1] = g.pre[i] + (int)nt;
+  }
+  for (size_t i = n; i < (size_t)pllm::kWgradGroupMax; ++i) g.pre[i + 1] = g.pre[n];
+  TORCH_CHECK(0 <= first && first <= last && last <= g.pre[n], "wgrad_group: tile range [", first, ", ", last,
+              ") of ", g.pre[n], " tiles");
+  g.first = (int)first;
+  g.last = (int)last;
+  const pllm::GemmSettings& s = pllm::gemm_settings();
+  const int grid = pllm::plan_grid(last - first, s.persistent ? pllm::grid_cap(s, pllm::gemm_cus()) : 1 << 30);
+  pllm::wgrad_pp_group(g, grid, cur_stream());
+}
+
 // ---------------------------------------------------------------- fused-epilogue GEMM
 // a [M, K] (row stride lda), b [N, K] contiguous -> [out [M, N], aux]:
 // epi 0: out = a b^T (+ bias); 1: out = gelu(pre), aux = pre = a b^T + bias; 2: out = relu(a b^T + bias);
@@ -1355,6 +1408,17 @@ TORCH_LIBRARY(pllm, m) {
         [](int64_t mf, int64_t gm, int64_t ph, int64_t rc, int64_t pe) {
           pllm::gemm_set_config((int)mf, (int)gm, (int)ph, (int)rc, (int)pe);
         });
+  m.def("wgrad_group(Tensor[] dys, Tensor[] xs, Tensor(a!)[] outs, Tensor(b!)[] biases, int[] overwrite, int first, int last) -> ()");
+  // wgrad_group_plan -> [tiles the grouped launch takes now from the head of a queue of problems with these
+  // tile counts / tiles per row band (done0 tiles of the first already run), its workgroups]
+  m.def("wgrad_group_plan(int[] tiles, int[] tiles_q, int done0) -> int[]",
+        [](at::IntArrayRef tiles, at::IntArrayRef tiles_q, int64_t done0) {
+          TORCH_CHECK(tiles.size() == tiles_q.size(), "wgrad_group_plan: one tiles_q per problem");
+          std::vector<int> t(tiles.begin(), tiles.end()), q(tiles_q.begin(), tiles_q.end());
+          const pllm::WgradGroupPlan p = pllm::wgrad_group_plan(pllm::gemm_settings(), pllm::gemm_cus(), t.data(),
+                                                                q.data(), (int)t.size(), (int)done0);
+          return std::vector<int64_t>{p.take, p.grid};
+        });
   m.def("wgrad_set_mfma(int mf) -> ()", [](int64_t mf) { pllm::wgrad_set_mfma((int)mf); });
   m.def("wgrad_set_hy(int on) -> ()", [](int64_t on) { pllm::wgrad_set_hy((int)on); });
   m.def("attn_bwd_set_workspace_mb(float mb) -> ()", [](double mb) { g_attn_ws_bytes = (int64_t)(mb * (1 << 20)); });
@@ -1399,6 +1463,7 @@ TORCH_LIBRARY_IMPL(pllm, CUDA, m) {
   m.impl("norm_bwd_acc", norm_bwd_acc_op);
   m.impl("bias_grad", bias_grad);
   m.impl("wgrad", wgrad);
+  m.impl("wgrad_group", wgrad_group);
   m.impl("gemm_tn", gemm_tn);
   m.impl("act_fwd", act_fwd);
   m.impl("act_bwd", act_bwd);

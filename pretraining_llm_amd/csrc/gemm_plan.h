@@ -189,4 +189,47 @@ inline WgradPlan wgrad_plan(const GemmSettings& s, int cus, int M, int P, int Q,
   return p;
 }
 
+// ---------------------------------------------------------------- grouped wgrad
+// Whole tiles of several queued weight gradients in one launch of the ping-pong kernel (wgrad_pp.hip's
+// grouped arm).  The queue is a list of problems in arrival order; its global tile list numbers every
+// problem's tiles row band by row band.  One launch runs a contiguous range of that list; what it leaves
+// stays queued for the next launch, or -- at the end of a backward -- goes to wgrad_plan one problem at a
+// time (slices, slabs and reduces as for an immediate call).
+constexpr int kWgradGroupMax = 16;  // problems one launch carries in its kernel argument
+
+struct WgradGroupPlan {
+  int take;  // tiles to launch now, counted from the head of the queue (0: keep waiting)
+  int grid;  // workgroups of that launch
+};
+
+// tiles[i] / tiles_q[i]: tile count and tiles per row band of queued problem i (n problems); done0: tiles of
+// problem 0 that an earlier launch ran (a multiple of tiles_q[0]).  The launch takes the whole rounds of the
+// grid -- ctas workgroups, the CUs less reserve_cus whether the grid is persistent or one workgroup per tile --
+// that the queue holds.  A cut inside a problem moves down to its last row-band boundary, so the part left
+// over is a [rows, Q] problem of its own for wgrad_plan (and a row band's bias column sums are complete in the
+// launch that runs it); a launch carries at most kWgradGroupMax problems.
+inline WgradGroupPlan wgrad_group_plan(const GemmSettings& s, int cus, const int* tiles, const int* tiles_q, int n,
+                                       int done0) {
+  WgradGroupPlan g{0, 0};
+  const int ctas = cus - s.reserve_cus > 8 ? cus - s.reserve_cus : 8;
+  int64_t total = -(int64_t)done0;
+  for (int i = 0; i < n; ++i) total += tiles[i];
+  if (!s.wgrad_pp || total < ctas) return g;
+  const int64_t want = total / ctas * ctas;
+  int64_t take = 0;
+  for (int i = 0; i < n && i < kWgradGroupMax && take < want; ++i) {
+    const int off = i == 0 ? done0 : 0;
+    const int64_t have = tiles[i] - off;
+    if (take + have <= want) {
+      take += have;
+    } else {
+      take += (want - take) / tiles_q[i] * tiles_q[i];
+      break;
+    }
+  }
+  g.take = (int)take;
+  g.grid = s.persistent ? (int)std::min<int64_t>(take, ctas) : (int)take;
+  return g;
+}
+
 }  // namespace pllm

@@ -178,6 +178,26 @@ bool wgrad(const WgradPlan& p, const void* dy, int64_t lda, const void* x, int64
 // its ordered fix-up
 void wgrad_pp(const WgradPlan& p, const void* dy, int64_t lda, const void* x, int64_t ldb, int M, int P, int Q,
               float* part, float* out, bool accumulate, float* bpart, hipStream_t st);
+// wgrad_pp.hip, grouped arm: whole tiles [first, last) of the global tile list of up to kWgradGroupMax problems
+// (pre[i]: index of problem i's first tile, pre[np] the total; a problem's tiles row band by row band), each tile
+// stored into / added to its problem's fp32 gradient by the workgroup that ran all its K-tiles.  bias_out (or
+// null): the problem's fp32 bias gradient, which the first Q tile of every row band adds its column sums to.
+// The argument travels by value: no table in device memory, nothing for a graph capture to re-read.
+struct WgradGroupProblem {
+  const void* A;  // dY [M, P], row stride lda
+  const void* B;  // X [M, Q], row stride ldb
+  int64_t lda, ldb;
+  float* out;       // [P, Q]
+  float* bias_out;  // [P] or null
+  int M, P, Q;
+  int accumulate;   // out += tile (else out = tile)
+};
+struct WgradGroup {
+  WgradGroupProblem p[kWgradGroupMax];
+  int pre[kWgradGroupMax + 1];
+  int np, first, last;
+};
+void wgrad_pp_group(const WgradGroup& g, int grid, hipStream_t st);
 
 // transpose.hip: desc int64 [n][6] = (src, dst, rows, cols, first tile, tiles per row band)
 int transpose_tiles(int R, int C);

@@ -28,6 +28,20 @@
 //    fp32 per lane and accumulator straight from registers (slab partial, or added to the gradient);
 //  * bias gradient (dY column sums) by all-ones MFMAs against the dY fragments on the first Q tile's
 //    items, each wave taking the row tiles jj == wc of its row halves (+4 MFMAs per 64).
+//
+// Grouped arm (wgrad_pp_group_kernel): one layer's gradient has fewer tiles than the GPU has CUs (a GPT-2 small
+// block: 27 + 9 + 36 + 36), which is why a launch of its own is cut along the tokens into fp32 slabs plus a
+// reduce pass.  Nothing reads a weight gradient before the optimizer, so ops queues the layers' problems and
+// launches whole rounds of the grid over the queue's tile list: each work item is one whole tile of one of up
+// to kWgradGroupMax problems (all K-tiles in one workgroup, stored or added to the gradient once), no slab and
+// no reduce; the bias column sums of a row band's first tile go straight from the accumulators into the bias
+// gradient.  The main loop, the K-tile sequence and the epilogue are the single-problem kernel's (bias path
+// compiled in, per item); only the item -> (problem, tile) step differs, a scalar walk over a prefix array
+// that travels in the kernel argument.  The host plan (gemm_plan.h wgrad_group_plan) cuts the launches at whole
+// rounds, and inside a problem at row-band boundaries, so whatever is left at the end of a backward is a [rows, Q]
+// problem for the single-problem plan above.  GPT-2 small at 64 x 1024 tokens: 48 GEMM + 60 reduce launches
+// per step become 5 grouped launches + 1 sliced remainder, the block weight gradients 10.2 -> 9.0 ms per step
+// (profiles/wgrad_grouped.md).
 // Requires M % 64 == 0, P % 8 == 0, Q % 8 == 0, row strides % 8 == 0 (checked by the binding).
 #include <algorithm>
 
@@ -410,6 +424,142 @@ __global__ __launch_bounds__(WNT) void wgrad_pp_kernel(WPArgs g) {
   if (c.wr == 0) wp_barrier();  // balance the stagger
 }
 
+// ---- grouped arm: whole tiles of several problems -------------------------------------------------------
+// per-lane DMA source offsets of this wave's pieces for row strides lda / ldb (see wgrad_pp_kernel)
+PL_DEV void wp_set_vo(WPCtx& c, int64_t lda, int64_t ldb) {
+  auto vo = [&](int img, int q, int64_t ld) {
+    const int row = 16 * (2 * (c.w & 1) + q) + (c.lane >> 2);
+    const int col = 32 * (img & 7) + 8 * ((c.lane & 3) ^ wp_swz(row));
+    return (uint32_t)(((int64_t)row * ld + col) * 2);
+  };
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    c.vo[0][q] = vo(wp_img<0>(c.w), q, lda);
+    c.vo[1][q] = vo(wp_img<1>(c.w), q, ldb);
+  }
+}
+
+// global tile t of the group -> its problem, as the single-problem kernel sees one (S = 1: whole tiles
+// into the gradient), its bias target and its segment (all K-tiles, dest -1).  A scalar walk over the
+// prefix array; every value here is wave-uniform.
+PL_DEV void wg_item(const pllm::WgradGroup& G, int t, WPArgs& a, float*& bias_out, WPSeg& s) {
+  int k = 0;
+#pragma unroll
+  for (int i = 1; i < pllm::kWgradGroupMax; ++i)
+    if (i < G.np && t >= G.pre[i]) k = i;
+  const pllm::WgradGroupProblem& p = G.p[k];
+  a.A = (const uint16_t*)p.A;
+  a.B = (const uint16_t*)p.B;
+  a.lda = p.lda;
+  a.ldb = p.ldb;
+  a.M = p.M;
+  a.P = p.P;
+  a.Q = p.Q;
+  a.S = 1;
+  a.slice_kt = p.M / WBK;
+  a.part = nullptr;
+  a.out = p.out;
+  a.accumulate = p.accumulate;
+  a.bpart = nullptr;
+  a.hy_full = a.hy_rem = a.hy_s = 0;
+  a.kst = p.M / WBK;
+  bias_out = p.bias_out;
+  const int tiles_q = (p.Q + WT - 1) / WT, lt = t - G.pre[k];
+  s.tp = lt / tiles_q;
+  s.tq = lt - s.tp * tiles_q;
+  s.kb = 0;
+  s.ke = a.kst;
+  s.dest = -1;
+  s.sidx = 0;
+}
+
+// The main loop, K-tile sequence and epilogue of wgrad_pp_kernel<true>, with the work item resolved to a
+// problem first: item lid + i G of the launch is global tile first + lid + i G.  The DMA of a tile's last
+// K-tile fetches the next item's first K-tile, so the per-lane source offsets (row strides) switch to the
+// next problem's just before it.  The bias column sums of a row band's first Q tile cover every token (the
+// tile is whole), so they are added to the bias gradient straight from the accumulators.
+__global__ __launch_bounds__(WNT) void wgrad_pp_group_kernel(pllm::WgradGroup G) {
+  __shared__ __attribute__((aligned(1024))) uint16_t smem[2 * WSLOT];
+  const int NG = gridDim.x;
+  const int lid = xcd_remap(blockIdx.x, NG);
+  const int items = G.last - G.first;
+  const int R = lid < items ? (items - lid + NG - 1) / NG : 0;
+  if (R == 0) return;
+  WPArgs g;
+  WPSeg sg;
+  float* bout;
+  wg_item(G, G.first + lid, g, bout, sg);
+  WPCtx c;
+  c.g = &g;
+  const int tid = threadIdx.x, lane = tid & 63;
+  c.w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  c.wr = c.w >> 2;
+  c.wc = c.w & 3;
+  c.lane = lane;
+  c.lds = (unsigned)(uintptr_t)smem;
+  wp_set_vo(c, g.lda, g.ldb);
+  {
+    const int gq = lane >> 4, tq = (lane & 15) >> 2, tpl = lane & 3;
+    const int row = 8 * gq + tq;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int col = 16 * h + 4 * tpl;
+      c.rd[h] = (unsigned)(row * 32 + ((((col >> 3) ^ wp_swz(row))) << 3) + (col & 7)) * 2u;
+    }
+  }
+  {
+    const WPSrd srd = wp_srds(g, sg.tp, sg.tq, sg.kb);
+    wp_issue<0>(c, srd, 0);
+    wp_issue<1>(c, srd, 0);
+    wp_issue<2>(c, srd, 0);
+    wp_issue<3>(c, srd, 0);
+  }
+  wp_vmwait<0>();
+  wp_barrier();
+  if (c.wr == 1) wp_barrier();  // the stagger: rows 128-255 run one barrier behind rows 0-127
+
+  f32x4 acc[4][8];
+  bf16x8 fa[2][4];
+  bf16x8 fb[2][2][2];
+  int s = 0;
+  for (int i = 0; i < R; ++i) {
+    const bool dob = bout != nullptr && sg.tq == 0;
+    f32x4 bacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+    const bool more = i + 1 < R;
+    for (int kt = sg.kb; kt < sg.ke; ++kt, ++s) {
+      WPSrd srd;
+      if (kt + 1 < sg.ke) {
+        srd = wp_srds(g, sg.tp, sg.tq, kt + 1);
+      } else if (more) {
+        WPArgs gn;
+        WPSeg sn;
+        float* bout_n;
+        wg_item(G, G.first + lid + (i + 1) * NG, gn, bout_n, sn);
+        srd = wp_srds(gn, sn.tp, sn.tq, sn.kb);
+        wp_set_vo(c, gn.lda, gn.ldb);
+      } else {
+        srd = WPSrd{srd_of(g.A, 0u), srd_of(g.B, 0u)};
+      }
+      if (kt == sg.kb) wp_ktile<true, true>(c, acc, fa, fb, bacc, dob, smem, s, srd);
+      else wp_ktile<false, true>(c, acc, fa, fb, bacc, dob, smem, s, srd);
+    }
+    wp_epilogue<false>(c, acc, sg);
+    if (dob) {
+      // P rows wr 128 + 16 (4 jh + wc) + lane, from lanes 0-15: db[row] += the tile's column sum
+      const __amdgpu_buffer_rsrc_t brs = wp_rsrc(bout, g.P * 4);
+#pragma unroll
+      for (int jh = 0; jh < 2; ++jh) {
+        const int prow = sg.tp * WT + c.wr * 128 + 16 * (4 * jh + c.wc) + lane;
+        const uint32_t bo = ((lane >> 4) == 0 && prow < g.P) ? (uint32_t)prow * 4u : kOff;
+        const float old = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(brs, bo, 0, 0));
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, old + bacc[jh][0]), brs, bo, 0, 0);
+      }
+    }
+    if (more) wg_item(G, G.first + lid + (i + 1) * NG, g, bout, sg);
+  }
+  if (c.wr == 0) wp_barrier();  // balance the stagger
+}
+
 // hybrid fix-up: the last hy_rem tiles get out (+)= their hy_s pieces in slice order; one block per
 // (tile, 4 rows), one 16-B column group per thread (all of a thread's loads independent)
 __global__ __launch_bounds__(256) void wgrad_hy_reduce_kernel(const float* __restrict__ part, float* __restrict__ out,
@@ -460,6 +610,11 @@ void wgrad_pp(const WgradPlan& p, const void* dy, int64_t lda, const void* x, in
   if (p.hy_rem > 0)
     hipLaunchKernelGGL(wgrad_hy_reduce_kernel, dim3(p.hy_rem, WT / 4), dim3(256), 0, st, part, out, P, Q,
                        (Q + WT - 1) / WT, p.hy_full, p.hy_rem, p.hy_s, g.accumulate);
+}
+
+void wgrad_pp_group(const WgradGroup& g, int grid, hipStream_t st) {
+  if (grid <= 0 || g.last <= g.first) return;
+  hipLaunchKernelGGL(wgrad_pp_group_kernel, dim3(grid), dim3(WNT), 0, st, g);
 }
 
 }  // namespace pllm

@@ -98,6 +98,8 @@ def _take(*params, whole: bool = False):
     ``whole``: the writer produces the entire gradient (the weight-gradient GEMM, ``qk_norm_bwd_``,
     ``attn_sink_bwd``) -> (slots, overwrite): with every slot fresh nothing is zeroed and the kernel stores
     instead of adding -- no zero fill, no read of zeros; else the fresh ones are zeroed and it adds."""
+    if any(getattr(p, "_pllm_wgrad_queued", False) for p in params):
+        wgrad_flush()  # a queued weight gradient (deferred mode of _weight_grad) lands before the next writer's
     slots, overwrite = tuple(_slot(p) for p in params), False
     if any(s is None and p is not None for s, p in zip(slots, params)):
         slots = (None,) * len(params)
@@ -147,11 +149,10 @@ def _linear_param_grads(dy2, x2, w, b, need_w: bool = True, need_b: bool = True,
         (tgt,), fresh = _take(w, whole=True)
         # (no weight slot: no fused bias target either, the bias takes the separate pass below)
         (btgt,) = _take(b) if need_b and fuse_bias and tgt is not None and FUSED_WGRAD_BIAS else (None,)
-        dw = _weight_grad(dy2, x2, tgt, btgt, overwrite=fresh)
-        if tgt is not None:
-            _wrote(w)
+        # (told of their slots' writes by _weight_grad: at once, or after the queued launch that completes them)
+        dw = _weight_grad(dy2, x2, tgt, btgt, overwrite=fresh,
+                          notify=(w if tgt is not None else None, b if btgt is not None else None))
         if btgt is not None:
-            _wrote(b)
             need_b = False
     if need_b:
         db = _bias_param_grad(dy2, b)
@@ -263,11 +264,15 @@ def _dgrad(dy, weight):
     return dy @ (wt.t() if wt is not None else weight)
 
 
-def _weight_grad(dy2, x2, tgt, btgt=None, overwrite: bool = False):
+def _weight_grad(dy2, x2, tgt, btgt=None, overwrite: bool = False, notify=()):
     """dW = dy2^T @ x2, added into ``tgt`` (bf16 or fp32) when given (returns None) else returned;
     ``overwrite``: stored into ``tgt`` instead (its first write of the step, ``_take(.., whole=True)``).
     ``btgt`` (with ``tgt``): the bias gradient (column sums of dy2) is added into it as well -- on the
-    hand-written kernel inside the GEMM (its all-ones MFMAs), else by the bias_grad kernels."""
+    hand-written kernel inside the GEMM (its all-ones MFMAs), else by the bias_grad kernels.
+    ``notify``: the parameters whose slots ``tgt`` / ``btgt`` are, told (``_wrote``, in this order) once the
+    slots hold the result -- before this returns, or, in the DEFERRED mode, later: a call with ``notify`` that
+    the hand-written kernel serves with fp32 slots may be queued (``_WgradQueue``, when ``_wgrad_defer_on``)
+    and run with other layers' as whole tiles of one grouped launch."""
     hip_ok = dy2.shape[1] % 8 == 0 and x2.shape[1] % 8 == 0 and dy2.shape[0] % 64 == 0
     f32_tgt = tgt is not None and tgt.dtype == torch.float32 and dy2.dtype != torch.float32
     # an fp32 gradient target always takes the hand-written kernel (fp32 read-add-write epilogue)
@@ -276,7 +281,12 @@ def _weight_grad(dy2, x2, tgt, btgt=None, overwrite: bool = False):
     if use_hip:
         dy2, x2 = dy2.contiguous(), x2.contiguous()
         if tgt is not None:
-            _ops().wgrad(dy2, x2, tgt.view(dy2.shape[1], x2.shape[1]), btgt, overwrite)
+            out = tgt.view(dy2.shape[1], x2.shape[1])
+            if (notify and f32_tgt and (btgt is None or btgt.dtype == torch.float32) and _wgrad_defer_on(dy2)
+                    and _wgrad_sliced(dy2, x2, btgt) and _WGRAD_QUEUE.push(dy2, x2, out, btgt, overwrite, notify)):
+                return None
+            _ops().wgrad(dy2, x2, out, btgt, overwrite)
+            _wrote(*notify)
             return None
         return _ops().wgrad(dy2, x2)
     if btgt is not None:
@@ -290,8 +300,146 @@ def _weight_grad(dy2, x2, tgt, btgt=None, overwrite: bool = False):
             torch.mm(dy2.t(), x2, out=tgt.view(dy2.shape[1], x2.shape[1]))
         else:
             tgt.addmm_(dy2.t(), x2)
+        _wrote(*notify)
         return None
     return dy2.t() @ x2
+
+
+# ---------------------------------------------------------------------------
+# Deferred weight gradients.  Nothing reads a weight gradient before the optimizer, and one layer's GEMM has
+# fewer 256 x 256 output tiles than the GPU has CUs (a GPT-2 small block: 27 + 9 + 36 + 36), so alone it is
+# split along the tokens into fp32 slabs that a reduce pass sums.  Queued, the layers' tiles fill whole rounds
+# of the grid: each tile runs over all tokens in one workgroup and is written once (the grouped arm of
+# csrc/wgrad_pp.hip), with no slabs and no reduce.  Only what is left at the end of the backward -- less than
+# one round -- is sliced as before.  PLLM_AB wgrad_defer=0: every weight gradient at once.
+# ---------------------------------------------------------------------------
+WGRAD_DEFER = _ab("wgrad_defer", True)
+WGRAD_TILE = 256          # csrc/gemm_plan.h kPlanTile
+WGRAD_GROUP_MAX = 16      # csrc/gemm_plan.h kWgradGroupMax
+WGRAD_DEFER_MIN_SLICES = 2  # queue what the immediate plan would cut into this many token slices or more
+_wgrad_defer_engine = True  # wgrad_defer_allow: off while an engine launches collectives from gradient hooks
+
+
+def wgrad_defer_allow(on: bool) -> None:
+    """The data-parallel engines switch deferral off when they launch collectives from the parameters'
+    gradient notifications (more than one rank: a notification held back holds a bucket's all-reduce back,
+    and the grouped launch takes every CU), the single-rank optimizer switches it on."""
+    global _wgrad_defer_engine
+    wgrad_flush()
+    _wgrad_defer_engine = bool(on)
+
+
+def _wgrad_defer_on(dy2) -> bool:
+    """Deferred mode for this call: PLLM_AB wgrad_defer (default 1), the HIP path, one rank."""
+    if not (WGRAD_DEFER and _wgrad_defer_engine and _hip(dy2)) or dy2.shape[0] < 128:
+        return False
+    dist = torch.distributed
+    return not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+
+
+def _wgrad_sliced(dy2, x2, btgt) -> bool:
+    """Whether the immediate launch of this problem would be split along the tokens (``wgrad_plan``: at least
+    WGRAD_DEFER_MIN_SLICES slices).  Only those are queued: a problem that already runs as whole tiles writes
+    no slabs and has no reduce pass to save, so it runs in its layer's backward as before."""
+    S = _ops().wgrad_plan(dy2.shape[0], dy2.shape[1], x2.shape[1], True, btgt is not None)[1]
+    return S >= WGRAD_DEFER_MIN_SLICES
+
+
+class _WgradQueue:
+    """Queued weight-gradient problems (dy2, x2, out [P, Q] fp32, bias slot or None, overwrite, parameters to
+    tell) in arrival order, the operands held by reference.  Their tiles form one list, a problem's tiles row
+    band by row band; ``done0`` tiles of the first problem have run.  ``push`` launches the whole rounds of the
+    grid the queue holds (``torch.ops.pllm.wgrad_group_plan`` cuts them, at row-band boundaries inside a
+    problem) and keeps the rest; the flush at the end of the backward launches the last whole rounds and hands
+    what is left -- the unfinished row bands of the first problem as a [rows, Q] problem of their own, then the
+    others -- to ``torch.ops.pllm.wgrad``, sliced as an immediate call would be.  A parameter is told of its
+    slot's write after the launch that ran its problem's last tile, weight before bias, in queue order."""
+
+    def __init__(self):
+        self.items, self.done0, self.armed = [], 0, False
+
+    # the three calls into the extension (tests/test_wgrad_queue.py replaces them with recorders)
+    def plan(self, tiles, tiles_q, done0):
+        return _ops().wgrad_group_plan(tiles, tiles_q, done0)
+
+    def run_group(self, items, first, last):
+        empty = items[0][0].new_empty(0, dtype=torch.float32)
+        _ops().wgrad_group([it[0] for it in items], [it[1] for it in items], [it[2] for it in items],
+                           [empty if it[3] is None else it[3] for it in items], [int(it[4]) for it in items],
+                           first, last)
+
+    def run_single(self, dy2, x2, out, btgt, overwrite):
+        _ops().wgrad(dy2, x2, out, btgt, overwrite)
+
+    @staticmethod
+    def _tiles(it):
+        tq = -(-it[2].shape[1] // WGRAD_TILE)
+        return -(-it[2].shape[0] // WGRAD_TILE) * tq, tq
+
+    def push(self, dy2, x2, out, btgt, overwrite, notify) -> bool:
+        """Queue one problem -> False when no flush can be registered (not inside a backward): the caller
+        runs it at once."""
+        if not self.armed:
+            try:
+                torch.autograd.Variable._execution_engine.queue_callback(self.flush)
+            except RuntimeError:
+                return False
+            self.armed = True
+        for p in notify:
+            if p is not None:
+                p._pllm_wgrad_queued = True
+        self.items.append((dy2, x2, out, btgt, overwrite, tuple(notify)))
+        self._launch_rounds()
+        return True
+
+    def _done(self, it):
+        for p in it[5]:
+            if p is not None:
+                p._pllm_wgrad_queued = False
+        _wrote(*it[5])
+
+    def _launch_rounds(self):
+        while self.items:
+            head = self.items[:WGRAD_GROUP_MAX]
+            counts = [self._tiles(it) for it in head]
+            take = int(self.plan([c[0] for c in counts], [c[1] for c in counts], self.done0)[0])
+            if take <= 0:
+                return
+            first, last, n, end = self.done0, self.done0 + take, 0, 0
+            while n < len(head) and end < last:  # the problems the range touches
+                end += counts[n][0]
+                n += 1
+            self.run_group(head[:n], first, last)
+            whole = n if end == last else n - 1  # the last one touched may be cut
+            for it in head[:whole]:
+                self._done(it)
+            self.done0 = last - (end - counts[n - 1][0]) if whole < n else 0
+            del self.items[:whole]
+
+    def flush(self):
+        """Everything queued lands: whole rounds grouped, the rest one problem at a time."""
+        self.armed = False
+        if not self.items:
+            return
+        self._launch_rounds()
+        items, done0 = self.items, self.done0
+        self.items, self.done0 = [], 0
+        for i, it in enumerate(items):
+            dy2, x2, out, btgt, overwrite = it[:5]
+            if i == 0 and done0:  # its first row bands ran in a grouped launch: the rest as [rows, Q]
+                r0 = done0 // self._tiles(it)[1] * WGRAD_TILE
+                dy2, out, btgt = dy2[:, r0:], out[r0:], None if btgt is None else btgt[r0:]
+            self.run_single(dy2, x2, out, btgt, overwrite)
+            self._done(it)
+
+
+_WGRAD_QUEUE = _WgradQueue()
+
+
+def wgrad_flush() -> None:
+    """Run every queued weight gradient now.  Registered for the end of each backward through the autograd
+    engine's callback; every reader of the gradient slots in this package calls it first as well."""
+    _WGRAD_QUEUE.flush()
 
 
 # ---------------------------------------------------------------------------

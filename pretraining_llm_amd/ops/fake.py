@@ -54,6 +54,10 @@ def register() -> None:
             return dy.new_empty((0,))
         return dy.new_empty((dy.shape[1], x.shape[1]))
 
+    @_reg("wgrad_group")
+    def _(dys, xs, outs, biases, overwrite, first, last):
+        return None
+
     @_reg("zero_ranges_")
     def _(buf, ranges, total_len):
         return None

@@ -32,6 +32,7 @@ from typing import List, Optional
 import torch
 import torch.distributed as dist
 
+from .. import ops as _ops_mod
 from ..ab import ab as _ab
 
 
@@ -147,6 +148,8 @@ class DataParallelEngine:
         if broadcast_params and self.sync:
             dist.broadcast(optimizer.flat_param, src=self._global_src(), group=process_group)
             optimizer.sync_master_from_params()
+        if self.sync:
+            _ops_mod.wgrad_defer_allow(False)  # gradient notifications launch the buckets: none is held back
         if self.sync and overlap:
             for i, p in enumerate(params):
                 h = self._make_hook(i)
@@ -218,6 +221,7 @@ class DataParallelEngine:
     def finish_grad_sync(self):
         """Launch any bucket not yet launched (unused params, no-overlap mode) and wait for all.
         Returns the gradient scale the optimizer must apply (1/world)."""
+        _ops_mod.wgrad_flush()
         self.timer.backward_end()
         if self.sync:
             while self._next_launch < len(self.buckets):

@@ -327,6 +327,8 @@ class ZeroDataParallelEngine:
             src = dist.get_global_rank(self.pg, 0) if self.pg is not None else 0
             dist.broadcast(opt.flat_param, src=src, group=self.pg)
             opt.sync_master_from_params()
+        if self.world > 1:
+            _ops_mod.wgrad_defer_allow(False)  # (as DataParallelEngine: no notification held back)
         if self.world > 1 and overlap:
             for i, p in enumerate(params):
                 h = self._make_hook(i)
@@ -378,6 +380,7 @@ class ZeroDataParallelEngine:
             self.enabled = old
 
     def finish_grad_sync(self):
+        _ops_mod.wgrad_flush()
         self.timer.backward_end()
         opt = self.opt
         if self.world > 1:

@@ -167,6 +167,9 @@ class FlatAdamW:
             # replays would add onto the slots the partial zero_grad leaves alone
             for p in self._fresh_params:
                 p._pllm_grad_fresh = True
+        # one rank, no hook-launched collectives: the backward may queue its weight gradients for grouped
+        # whole-tile launches (ops._WgradQueue); a data-parallel engine that syncs switches this off again
+        _ops_mod.wgrad_defer_allow(True)
 
     def _clear_unwritten(self, idx=None):
         """Fresh slots no writer touched this step (an unused weight) hold last step's gradient: zero them.
@@ -175,6 +178,7 @@ class FlatAdamW:
         gradient into every replica -- parallel/dp.py DataParallel._launch).  A slot still reserved
         (ops._reserve: an LM-head forward under grad mode whose backward never ran) holds an unscaled partial
         gradient nobody finished: unwritten as well, and released."""
+        _ops_mod.wgrad_flush()  # (a no-op after a backward: its end flushed the queued weight gradients)
         if self.lazy_zero:
             params = self._fresh_params if idx is None else [self.params[i] for i in idx]
             for p in params:
